@@ -13,11 +13,19 @@ step    : one pass of the flow over the whole grid (all passes of the program).
 timing  : W untimed warmup steps, then exactly K steps on the production path (hipGraph
           replay of K-step kernel passes) bracketed by a barrier and a device-wide
           synchronize (hipDeviceSynchronize) on both sides; the max over ranks is reported. Inputs are resident in HBM
-          (generated on the device) before timing. Then the same K steps again, launched
-          eagerly with a HIP event pair around every step kernel on its own stream: the
-          kernel's average duration for the roofline object.
+          (generated on the device) before timing. A plain run stops there: it prints the
+          headline line (value, ms_per_step, config) and nothing else is measured.
+--full  : everything beside the headline. The conservation check (total before / after),
+          then the same K steps again, launched eagerly with a HIP event pair around every
+          step kernel on its own stream (the kernel's average duration for the roofline
+          object, HBM and VALU roofs), and the CPU baseline (N = 1).
+--dump-outputs DIR: after the timed steps, what the timed path left for its caller, as
+          float64 DIR/<name>.npy: attr<a>.npy, the attribute's grid -- whole while all
+          attributes fit DUMP_BYTES, else a fixed seeded sample of whole rows (first and last
+          row always) -- and sums.npy, the per-attribute sums over all owned cells. The
+          inputs are seeded by global cell index, so equal arguments give equal inputs.
 
-Launch: python bench.py [--gpus 1] [--steps 1000] [--warmup 50]
+Launch: python bench.py [--gpus 1] [--steps 1000] [--warmup 50] [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
         (--halo host: the host transport over gloo, N ranks on however many GPUs exist)
 """
@@ -42,6 +50,8 @@ import mpimodel as mm  # noqa: E402
 # (the same operation torch.cuda.synchronize performs).
 mm.lib()
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all attributes' rows together (limit: 64 MB)
+DUMP_SEED = 0x4D50494D
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md chip table)
 RATE = 0.1             # src/Main.cpp:33
 
@@ -76,7 +86,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: conservation check, per-kernel timing pass with "
+                         "the HBM / VALU rooflines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed path's final state to DIR/<name>.npy (float64; a "
+                         "seeded row sample of a grid too large for 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: leave the CPU baseline out")
     ap.add_argument("--self-halo", action="store_true",
                     help="N=1 only: run the RCCL halo path against itself (MM_SELF_HALO) to "
                          "price the exchange + interior/border split")
@@ -214,16 +231,16 @@ def valu_roof(passes, h, W, kern_avg_ms, lr_cycles=None):
             "frac": round(cyc / (kern_avg_ms * 1e-3 * 2.4e9), 4)}
 
 
-def make_line(*, workload, wl, N, ranks, H, W, h, na, steps, warmup, el, plan, info,
-              kern_ms, n_launch, timing_steps, bytes_per_launch, passes, traffic, cons, halo,
-              self_halo, lr_cycles=None, graph_captures_timed=None):
+def make_line(*, workload, wl, N, ranks, H, W, h, na, steps, warmup, el, plan, info, halo,
+              self_halo, kern_ms=None, n_launch=0, timing_steps=0, bytes_per_launch=0.0,
+              passes=None, traffic=None, cons=None, lr_cycles=None, graph_captures_timed=None):
     """The driver's JSON line (no I/O): value = whole-job GCUPS = all ranks' cell-updates /
-    the max-over-ranks wall time `el` of exactly `steps` steps."""
+    the max-over-ranks wall time `el` of exactly `steps` steps. The roofline object needs the
+    kernel timing pass (kern_ms ...), the check object the totals (cons): a plain run has
+    neither (--full)."""
     gcups = H * W * steps / el / 1e9
-    kern_avg_ms = kern_ms / max(n_launch, 1)
     spl = max(plan) if info["kernel"] in (2, 3) and plan else 1  # steps of the longest pass
     kname = {0: "mm_pass_kernel", 2: "mm_passk_kernel", 3: "mm_wide_kernel"}[info["kernel"]]
-    achieved = bytes_per_launch / (kern_avg_ms * 1e-3) / 1e9 if kern_ms > 0 else None
     if info["graph_state"] == 1:
         path = f"hipGraph replay ({info['graph_launches']} graph launches)"
     elif info["graph_state"] == -1:
@@ -258,7 +275,11 @@ def make_line(*, workload, wl, N, ranks, H, W, h, na, steps, warmup, el, plan, i
                    "parallelism": par,
                    "passes_per_step": info["n_passes"],
                    "rows_per_wave": info["rows_per_wave"]},
-        "roofline": {
+    }
+    if kern_ms is not None:
+        kern_avg_ms = kern_ms / max(n_launch, 1)
+        achieved = bytes_per_launch / (kern_avg_ms * 1e-3) / 1e9 if kern_ms > 0 else None
+        line["roofline"] = {
             "bound": "hbm",
             "achieved": round(achieved, 1) if achieved else None,
             "peak": HBM_PEAK_GBS,
@@ -273,16 +294,47 @@ def make_line(*, workload, wl, N, ranks, H, W, h, na, steps, warmup, el, plan, i
             # BASELINE.md's formula: GCUPS x 16 B x A / 8 TB/s (per GPU); above 1.0
             # when K steps share one HBM round trip (temporal blocking)
             "equivalent_frac": round(gcups / ranks["gpus"] * 16.0 * na / HBM_PEAK_GBS, 4),
-        },
-        "check": {"total_rel_drift": cons},
-    }
-    v = valu_roof(passes, h, W, kern_avg_ms, lr_cycles)
-    if v:
-        line["roofline"]["valu"] = v
+        }
+        v = valu_roof(passes, h, W, kern_avg_ms, lr_cycles)
+        if v:
+            line["roofline"]["valu"] = v
+    if cons is not None:
+        line["check"] = {"total_rel_drift": cons}
     if graph_captures_timed is not None:
         # graphs captured inside the timed region (0: every graph was prepared ahead)
         line["config"]["graph_captures_timed"] = graph_captures_timed
     return line
+
+
+def dump_rows(h, W, na):
+    """Owned rows --dump-outputs keeps of every attribute: all of them while the attributes
+    fit DUMP_BYTES together, else the first, the last and a fixed seeded choice between."""
+    import numpy as np
+    n = DUMP_BYTES // (8 * W * na)
+    if n >= h:
+        return np.arange(h)
+    n = max(n, 2)
+    mid = np.random.default_rng(DUMP_SEED).choice(h - 2, size=n - 2, replace=False) + 1
+    return np.sort(np.concatenate([[0, h - 1], mid]))
+
+
+def dump_outputs(eng, out_dir, suffix, reduce_every):
+    """--dump-outputs: the state the timed steps left (what download() / sums() hand the
+    caller), float64 .npy files. rows.npy holds the row numbers of the attr files' rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = dump_rows(eng.h, eng.W, eng.n_attr)
+    for a in range(eng.n_attr):
+        if len(rows) == eng.h:
+            v = eng.download(a)
+        else:
+            v = np.concatenate([eng.read_rows(int(r), 1, a) for r in rows])
+        np.save(os.path.join(out_dir, f"attr{a}{suffix}.npy"), v)
+    np.save(os.path.join(out_dir, f"rows{suffix}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, f"sums{suffix}.npy"), eng.sums())
+    n = eng.info()["hist_entries"]
+    if reduce_every and n:  # the per-step sums the run recorded: the last step's
+        np.save(os.path.join(out_dir, f"step_sums{suffix}.npy"), eng.sums_history(n)[-1])
 
 
 def gloo_exchange(rank, N):
@@ -319,9 +371,9 @@ def main():
     N = world
     host = N > 1 and args.halo == "host"
 
-    import torch
-    import torch.distributed as dist
-    if N > 1:
+    if N > 1:  # torch only as launcher and control plane: a single process needs none
+        import torch
+        import torch.distributed as dist
         dist.init_process_group("gloo")  # control plane (and the host halo); data on RCCL
 
     if wl["scaling"] == "weak":
@@ -375,12 +427,14 @@ def main():
 
     def global_total(e):
         # total over attributes and ranks: what the flows conserve (src/Model.hpp:95)
-        t = torch.tensor([float(sum(e.sums()))], dtype=torch.float64)
-        if N > 1:
-            dist.all_reduce(t)
+        s = float(sum(e.sums()))
+        if N == 1:
+            return s
+        t = torch.tensor([s], dtype=torch.float64)
+        dist.all_reduce(t)
         return float(t.item())
 
-    s_before = global_total(eng)
+    s_before = global_total(eng) if args.full else None
 
     # the timed run's one-time work -- its hipGraphs (both buffer parities) and the plan of
     # its eager passes -- done ahead (mm_prepare runs no step); then the warmup steps, which
@@ -409,23 +463,29 @@ def main():
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
-    s_after = global_total(eng)
+    s_after = global_total(eng) if args.full else None
     if args.dump:  # tests: this rank's slab after warmup + steps
         import numpy as np
         np.save(f"{args.dump}.rank{rank}.npy", np.stack([eng.download(a) for a in range(na)]))
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, "" if N == 1 else f".rank{rank}", reduce_every)
 
-    # kernel pass: the timed run's own passes (mm_pass_plan), repeated eagerly until at
-    # least 3 launches, each step kernel bracketed by HIP events on its stream -- the
-    # launches rocprofv3 averages
     plan = eng.pass_plan(args.steps)
-    reps = max(1, -(-3 // max(len(plan), 1)))
-    eng.set_timing(True)
-    for _ in range(reps):
-        run(args.steps, reduce_every)
-    n_launch, kern_ms, bytes_per_launch = eng.timing()
-    eng.set_timing(False)
+    full = {}
+    if args.full:
+        # kernel pass: the timed run's own passes (mm_pass_plan), repeated eagerly until at
+        # least 3 launches, each step kernel bracketed by HIP events on its stream -- the
+        # launches rocprofv3 averages
+        reps = max(1, -(-3 // max(len(plan), 1)))
+        eng.set_timing(True)
+        for _ in range(reps):
+            run(args.steps, reduce_every)
+        n_launch, kern_ms, bytes_per_launch = eng.timing()
+        eng.set_timing(False)
+        full = dict(kern_ms=kern_ms, n_launch=n_launch, timing_steps=reps * args.steps,
+                    bytes_per_launch=bytes_per_launch,
+                    passes=[(k, *eng.pass_kernel(k)) for k in plan] * reps)
     info = eng.info()
-    passes = [(k, *eng.pass_kernel(k)) for k in plan] * reps
     gpus = [dev] if N == 1 else None
     if N > 1:
         got = [None] * N
@@ -438,7 +498,7 @@ def main():
         traffic, traffic_src = None, None
         tf = os.path.join(REPO, "profiles", "pmc_traffic.json")
         # only when it was measured on this kernel and on the workload's own grid
-        if os.path.exists(tf) and not args.grid:
+        if args.full and os.path.exists(tf) and not args.grid:
             with open(tf) as f:
                 pmc = json.load(f)
             key = f"{args.workload}_n{N}_k{spl}"
@@ -457,15 +517,15 @@ def main():
                 cols, n_diff, n_tr, ck if k == info["steps_per_launch"] else 3)
         line = make_line(workload=args.workload, wl=wl, N=N, ranks={"gpus": len(set(gpus))},
                          H=H, W=W, h=h, na=na, steps=args.steps, warmup=args.warmup, el=el,
-                         plan=plan, info=info, kern_ms=kern_ms, n_launch=n_launch,
-                         timing_steps=reps * args.steps, bytes_per_launch=bytes_per_launch, passes=passes, traffic=traffic,
-                         cons=abs(s_after - s_before) / abs(s_before), halo=args.halo,
-                         self_halo=args.self_halo, lr_cycles=lr,
-                         graph_captures_timed=None if host else graphs_timed)
-        line["roofline"]["traffic_source"] = traffic_src
+                         plan=plan, info=info, traffic=traffic,
+                         cons=abs(s_after - s_before) / abs(s_before) if args.full else None,
+                         halo=args.halo, self_halo=args.self_halo, lr_cycles=lr,
+                         graph_captures_timed=None if host else graphs_timed, **full)
+        if args.full:
+            line["roofline"]["traffic_source"] = traffic_src
         if args.workload == "c5" and args.program != "c5":
             line["config"]["program"] = f"{args.program}: {flows}"
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl["rows"], W, args.cpu_seconds) \
                 if na == 1 else cpu_baseline_program(wl["rows"], W, na, flows,
                                                      args.cpu_seconds)

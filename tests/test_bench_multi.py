@@ -105,6 +105,31 @@ def test_valu_roof_four_attributes():
     assert d["config"]["graph_captures_timed"] == 0
 
 
+def test_line_plain_run():
+    """Without the kernel pass and the totals (a run without --full) the line is the
+    headline: the same value and ms_per_step, no roofline or check object."""
+    import bench
+    wl = bench.WORKLOADS["c3"]
+    kw = dict(workload="c3", wl=wl, N=1, ranks={"gpus": 1}, H=32768, W=32768, h=32768, na=1,
+              steps=20, warmup=5, el=0.01, plan=[20], info=INFO, halo="rccl", self_halo=False)
+    d = bench.make_line(**kw)
+    full, _, _, _ = line_for(bench, "c3", 1, gpus=1)
+    assert "roofline" not in d and "check" not in d and "cpu_baseline" not in d
+    assert {k: v for k, v in full.items() if k not in ("roofline", "check")} == d
+
+
+@pytest.mark.parametrize("h,W,na", [(32768, 32768, 1), (4096, 4096, 4), (300, 1000, 1)])
+def test_dump_rows(h, W, na):
+    """--dump-outputs keeps whole rows: every row of a small slab, else a fixed choice with
+    the first and the last row, all attributes within 64 MB."""
+    import bench
+    rows = bench.dump_rows(h, W, na)
+    assert np.array_equal(rows, bench.dump_rows(h, W, na))  # the same rows every run
+    assert np.array_equal(rows, np.unique(rows)) and rows[0] == 0 and rows[-1] == h - 1
+    assert len(rows) * W * 8 * na <= 64e6
+    assert len(rows) == h or len(rows) * W * 8 * na > 32e6
+
+
 def _exchange_worker(rank, world, port, out):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
@@ -149,7 +174,7 @@ def test_host_halo_bench_bit_exact(gpu, O, tmp_path, N, H, W, steps, workload):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", str(N), "--halo", "host",
            "--workload", workload, "--grid", str(H), str(W), "--steps", str(steps),
-           "--warmup", "0", "--dump", dump]
+           "--warmup", "0", "--dump", dump, "--full"]
     p = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=240,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

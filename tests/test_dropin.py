@@ -2,8 +2,9 @@
 the GPU under mpirun, and their output files are compared with the reference's.
 
 * oracle/_ref/dropin_ref_main is the reference's own src/Main.cpp, UNCHANGED, compiled
-  against our headers (mpi-model_amd/api/Makefile; built in the build container and kept
-  there, .gpurunignore -- on the GPU box these runs use examples/drop_in_main; the CPU test
+  against our headers (mpi-model_amd/api/Makefile; built only where the reference lies. It
+  finds the engine relative to its own path or through engine_env below, so it runs
+  wherever oracle/_ref/ comes along with the tree; without it these runs use examples/drop_in_main alone; the CPU test
   tests/test_abi.py::test_reference_main_compiles_and_links_unchanged compiles and links it).
 * examples/drop_in_main.cpp is our Main.cpp-style program.
 The reference writes ../output/comm_rank%d.txt per worker plus a merged file
@@ -26,13 +27,24 @@ pytestmark = pytest.mark.gpu
 MPIRUN = os.environ.get("MPIRUN", "/opt/conda/bin/mpirun")
 
 
+def engine_env(env=None):
+    """The tests' environment with this tree's engine on the loader's path: a program
+    reaches libmpimodel_hip.so through its own RPATH where it was built in place, and
+    through this where it was built elsewhere and came along with oracle/_ref/ (a copied or
+    linked directory, whose $ORIGIN is not this tree)."""
+    e = dict(os.environ)
+    e.update(env or {})
+    e["LD_LIBRARY_PATH"] = os.pathsep.join(
+        [os.path.join(REPO, "mpi-model_amd")] + [p for p in [e.get("LD_LIBRARY_PATH")] if p])
+    return e
+
+
 def run_mpi(tmp_path, binary, np_, args=(), timeout=120, env=None):
     run = tmp_path / "run"
     out = tmp_path / "output"
     run.mkdir()
     out.mkdir()
-    e = dict(os.environ)
-    e.update(env or {})
+    e = engine_env(env)
     p = subprocess.run([MPIRUN, "-np", str(np_), binary] + [str(a) for a in args], cwd=run,
                        capture_output=True, text=True, timeout=timeout, env=e)
     assert p.returncode == 0, p.stdout + p.stderr

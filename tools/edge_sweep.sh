@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 D=${D:-gpurun_out/edge}; mkdir -p $D
 one() {  # tag edge args...
     local tag=$1 e=$2; shift 2
-    MM_SEG_EDGE=$e timeout -k 10 300 python3 -u bench.py "$@" --no-cpu-baseline > $D/${tag}_e$e.log 2>&1 || exit 3
+    MM_SEG_EDGE=$e timeout -k 10 300 python3 -u bench.py "$@" --full --no-cpu-baseline > $D/${tag}_e$e.log 2>&1 || exit 3
     python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); print(sys.argv[2], d['value'], d['roofline']['kernel_avg_us'])" $D/${tag}_e$e.log "$tag edge=$e"
 }
 if [ "${ONLY:-}" = c5 ]; then  # the four-attribute line alone

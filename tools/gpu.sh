@@ -2,7 +2,7 @@
 # The one GPU runner of this repository (replaces the per-round one-off scripts).
 #
 #   bash tools/gpu.sh test [pytest args]      GPU test suite (pytest -m gpu), then smoke()
-#   bash tools/gpu.sh bench WL STEPS WARMUP [bench.py args]   one bench.py line
+#   bash tools/gpu.sh bench WL STEPS WARMUP [bench.py args]   one bench.py --full line
 #   bash tools/gpu.sh lines                   every workload's bench line: the driver's
 #                                             command (c3, 20 steps) and 1000-step c2..c5
 #   bash tools/gpu.sh prof NAME WL STEPS WARMUP [bench.py args]
@@ -57,7 +57,7 @@ bench() {  # WL STEPS WARMUP [args]
     local wl=$1 steps=$2 warm=$3
     shift 3
     local log="$D/bench_${wl}_${steps}${TAG:+_$TAG}.log"
-    timeout -k 10 600 python3 -u bench.py --workload "$wl" --steps "$steps" --warmup "$warm" "$@" \
+    timeout -k 10 600 python3 -u bench.py --full --workload "$wl" --steps "$steps" --warmup "$warm" "$@" \
         > "$log" 2>&1 || fail "bench $wl" $? "$log"
     grep '^{' "$log"
 }
@@ -73,7 +73,7 @@ lines() {
 prof() {  # NAME WL STEPS WARMUP [args]
     local name=$1 wl=$2 steps=$3 warm=$4
     shift 4
-    local out="$D/prof_$name" args="--workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
+    local out="$D/prof_$name" args="--full --workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
     mkdir -p "$out"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run \
         -- python3 bench.py $args > "$out/trace.log" 2>&1 || fail "prof trace $name" $? "$out/trace.log"
@@ -90,7 +90,7 @@ trace() {  # NAME WL STEPS WARMUP [args]
     local out="$D/trace_$name"
     mkdir -p "$out"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o run \
-        -- python3 bench.py --workload "$wl" --steps "$steps" --warmup "$warm" --no-cpu-baseline "$@" \
+        -- python3 bench.py --full --workload "$wl" --steps "$steps" --warmup "$warm" --no-cpu-baseline "$@" \
         > "$out/trace.log" 2>&1 || fail "trace $name" $? "$out/trace.log"
     grep '^{' "$out/trace.log" | cut -c1-200
 }
@@ -99,7 +99,7 @@ sq() {  # NAME WL STEPS WARMUP [args]: SQ wave-cycle split + effective clock (on
         # 6 SQ + 1 GRBM counters fit gfx950's slots), after a trace run for the kernel time
     local name=$1 wl=$2 steps=$3 warm=$4
     shift 4
-    local out="$D/sq_$name" args="--workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
+    local out="$D/sq_$name" args="--full --workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
     mkdir -p "$out"
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run \
         -- python3 bench.py $args > "$out/trace.log" 2>&1 || fail "sq trace $name" $? "$out/trace.log"
@@ -114,7 +114,7 @@ sq() {  # NAME WL STEPS WARMUP [args]: SQ wave-cycle split + effective clock (on
 pmc() {  # NAME WL STEPS WARMUP "COUNTERS" [args]: one --pmc pass of up to 8 SQ counters
     local name=$1 wl=$2 steps=$3 warm=$4 counters=$5
     shift 5
-    local out="$D/pmc_$name" args="--workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
+    local out="$D/pmc_$name" args="--full --workload $wl --steps $steps --warmup $warm --no-cpu-baseline $*"
     mkdir -p "$out"
     timeout -s KILL 300 rocprofv3 --pmc $counters --output-format csv -d "$out/pmc" -o run \
         -- python3 bench.py $args > "$out/pmc.log" 2>&1 || fail "pmc $name" $? "$out/pmc.log"
@@ -166,7 +166,7 @@ trace20() {  # HIP-runtime + kernel trace of one 20-step split run (launch-to-st
     local out="$D/hiptrace20"
     mkdir -p "$out"
     timeout -k 10 300 rocprofv3 --hip-trace --kernel-trace --output-format csv -d "$out" -o run \
-        -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --grid 8192 32768 --self-halo \
+        -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --grid 8192 32768 --self-halo \
         > "$out/trace.log" 2>&1 || fail trace20 $? "$out/trace.log"
     python3 tools/launch_latency.py "$out" > "$out/launch_latency.txt" && cat "$out/launch_latency.txt"
 }
@@ -223,7 +223,7 @@ scale() {  # WL [N...]
         local log="$D/scale_${wl}_n$n.log"
         timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" \
             --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus "$n" \
-            --workload "$wl" --steps 20 --warmup 5 > "$log" 2>&1 || fail "scale $wl N=$n" $? "$log"
+            --workload "$wl" --steps 20 --warmup 5 --full > "$log" 2>&1 || fail "scale $wl N=$n" $? "$log"
         grep '^{' "$log"
     done
 }
