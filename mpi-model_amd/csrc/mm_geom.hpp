@@ -1,0 +1,52 @@
+// mm_geom.hpp -- the kernels' geometry as plain arithmetic: constants and per-instance
+// shapes that both the kernel units (through mm_internal.hpp) and the host-only planner
+// (mm_plan.cpp) need. No HIP include; a unit whose tuning macro fixes one of these values
+// static_asserts that it agrees.
+#pragma once
+
+namespace mm {
+
+constexpr int kMaxAttr = 4;     // SoA attributes per fused pass (config C5: 4)
+constexpr int kMaxChain = 4;    // elementwise transfers before / after a pass's diffusion
+                                // (a longer chain starts a new pass; 4 holds config C5's
+                                // chain and, against 8, frees kernel-argument SGPRs: C5 -8 %)
+constexpr int kStripCols = 128; // columns per wave: 64 lanes x double2 (16 B per lane)
+constexpr int kWavesPerBlock = 4;
+constexpr int kBlock = 64 * kWavesPerBlock;
+constexpr int kMaxSteps = 10;    // fused steps per pass of mm_passk_kernel (one attribute)
+constexpr int kMaxWide = 20;     // fused steps per pass of mm_wide_kernel (one attribute)
+constexpr int kGhost = kMaxWide;  // ghost rows above and below a slab (K fused steps need K)
+constexpr int kBorderRows = 4;     // rows per wave of the K-step kernel's border launches
+constexpr int kSegPrefetch1 = 8;   // mm_passk.hpp seg_prefetch<1>() (MM_SEG_U1)
+constexpr int kWide20Waves = 4;    // waves per workgroup, K = 20 (mm_wide_k20.hip: 20 / MM_K20_KW)
+constexpr int kWideRingWaves = 4;  // the ring instance (mm_widear_k8.hip: 8 / MM_WIDEAR_KW)
+
+inline int passk_out_cols(int k) { return kStripCols - 4 * ((k + 1) / 2); }
+
+inline int passk_max_steps(int na) { return na == 1 ? kMaxSteps : 2; }
+
+// largest segment (rows) whose buffer offsets stay below 2^31 at this pitch
+inline long long passk_max_rows(int k, long long pitch) {
+    // every buffer offset of a wave (rows x pitch x 8 B, plus the OOB marker) stays < 2^31
+    return (1LL << 31) / (pitch * 8) - (3 * k + 2 * kSegPrefetch1 + 8);
+}
+
+inline bool wide_has(int k, int c, int na) {
+    if (na > 1) return na == 4 && c == 2 && (k == 4 || k == 8);
+    return c == 4 && (k == 4 || k == 8 || k == 12 || k == 16 || k == 20);
+}
+
+inline int wide_out_cols(int k, int c) {
+    return 64 * c - 2 * c * ((k + c - 1) / c);  // 64 lanes less ceil(K / C) halo lanes a side
+}
+
+inline int wide_waves_per_block(int k, int c, int na, bool ring) {
+    if (!wide_has(k, c, na)) return 0;
+    if (na > 1 && k == 8 && ring) return kWideRingWaves;
+    if (na == 1 && k == 20) return kWide20Waves;
+    // one attribute: K / 4 levels per wave, 4 level groups; four attributes: mm_widea_k4
+    // 1 level per wave, mm_widea_k8 2
+    return 4;
+}
+
+}  // namespace mm

@@ -4,19 +4,9 @@
 
 #include <hip/hip_runtime.h>
 
-namespace mm {
+#include "mm_geom.hpp"  // the constants and the kernels' geometry (hip-free)
 
-constexpr int kMaxAttr = 4;     // SoA attributes per fused pass (config C5: 4)
-constexpr int kMaxChain = 4;    // elementwise transfers before / after a pass's diffusion
-                                // (a longer chain starts a new pass; 4 holds config C5's
-                                // chain and, against 8, frees kernel-argument SGPRs: C5 -8 %)
-constexpr int kStripCols = 128; // columns per wave: 64 lanes x double2 (16 B per lane)
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = 64 * kWavesPerBlock;
-constexpr int kMaxSteps = 10;    // fused steps per pass of mm_passk_kernel (one attribute)
-constexpr int kMaxWide = 20;     // fused steps per pass of mm_wide_kernel (one attribute)
-constexpr int kGhost = kMaxWide;  // ghost rows above and below a slab (K fused steps need K)
-constexpr int kBorderRows = 4;     // rows per wave of the K-step kernel's border launches
+namespace mm {
 
 // One fused Jacobi pass over a row slab. Every buffer pointer points at owned row 0;
 // rows -kGhost..-1 and h..h+kGhost-1 are ghost rows; local row r is global x_init+r.
@@ -55,10 +45,6 @@ hipError_t launch_pass(int na, bool reduce, const PassArgs& a, hipStream_t s, in
 // blocks (a.th = 4). a.nstrips = ceil(W / passk_out_cols(k)). red: every level's sums into
 // partials[wave][k][na]. variant bit 0: non-temporal stores.
 hipError_t launch_passk(int k, int na, bool red, const PassArgs& a, hipStream_t s, int variant);
-int passk_out_cols(int k);
-int passk_max_steps(int na);
-// largest segment (rows) whose buffer offsets stay below 2^31 at this pitch
-long long passk_max_rows(int k, long long pitch);
 // resident waves per CU of the segment kernel (occupancy API), 0 if unknown
 int passk_waves_per_cu(int k, int na, bool red, int nt);
 // Level-split K-step kernel (mm_wide_kernel) of a one-pass program with na attributes and
@@ -72,9 +58,6 @@ int passk_waves_per_cu(int k, int na, bool red, int nt);
 // compile-time-chain instance); bit 2: the pass has a post-chain (K = 8: the instance
 // that runs one); bits 4-6: K = 8, four attributes: the pass's attributes 0..N-1 diffuse,
 // the others do not (the engine relabels them so; the instance has N at compile time).
-bool wide_has(int k, int c, int na);
-int wide_out_cols(int k, int c, int na);
-int wide_waves_per_block(int k, int c, int na, bool ring);
 int wide_blocks_per_cu(int k, int c, int na, bool red, int nt);
 hipError_t launch_wide(int k, int c, int na, bool red, const PassArgs& a, hipStream_t s,
                        int variant);

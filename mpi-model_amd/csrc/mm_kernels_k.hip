@@ -64,14 +64,7 @@ hipError_t launch_finalize_levels(const double* partials, long long n, int k, in
     return hipGetLastError();
 }
 
-int passk_out_cols(int k) { return kStripCols - 4 * ((k + 1) / 2); }
-
-int passk_max_steps(int na) { return na == 1 ? kMaxSteps : 2; }
-
-long long passk_max_rows(int k, long long pitch) {
-    // every buffer offset of a wave (rows x pitch x 8 B, plus the OOB marker) stays < 2^31
-    return (1LL << 31) / (pitch * 8) - (3 * k + 2 * seg_prefetch<1>() + 8);
-}
+static_assert(seg_prefetch<1>() == kSegPrefetch1, "mm_geom.hpp: passk_max_rows counts MM_SEG_U1 rows");
 
 int passk_waves_per_cu(int k, int na, bool red, int nt) {
     switch (k) {
@@ -107,25 +100,6 @@ hipError_t launch_passk(int k, int na, bool red, const PassArgs& a, hipStream_t 
         case 10: return passk_launch_k10(na, red, a, s, variant);
         default: return hipErrorInvalidValue;
     }
-}
-
-bool wide_has(int k, int c, int na) {
-    if (na > 1) return na == 4 && c == 2 && (k == 4 || k == 8);
-    return c == 4 && (k == 4 || k == 8 || k == 12 || k == 16 || k == 20);
-}
-
-int wide_out_cols(int k, int c, int na) {
-    (void)na;
-    return 64 * c - 2 * c * ((k + c - 1) / c);  // 64 lanes less ceil(K / C) halo lanes a side
-}
-
-int wide_waves_per_block(int k, int c, int na, bool ring) {
-    if (!wide_has(k, c, na)) return 0;
-    if (na > 1 && k == 8 && ring) return widear_waves_k8();
-    if (na == 1 && k == 20) return wide_waves_k20();  // MM_K20_KW levels per wave
-    // one attribute: K / 4 levels per wave, 4 level groups; four attributes: mm_widea_k4
-    // 1 level per wave, mm_widea_k8 2
-    return 4;
 }
 
 namespace {

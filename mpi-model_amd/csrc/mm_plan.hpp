@@ -1,0 +1,120 @@
+// mm_plan.hpp -- what a run does, decided from the slab's shape and the tuning variables:
+// which kernel runs a pass of K steps, how many steps each pass takes, how a pass's rows
+// are cut into segments and launches, how many steps a replayed graph holds. Plain
+// arithmetic: no HIP, no engine; mm_engine.hip launches what this describes, and
+// tests/test_plan.py checks it without a GPU. Every rank of a chain must plan the same
+// passes (or the K-row exchanges would not pair up), so nothing here reads the rank or
+// this slab's own rows where the chain's thinnest slab (min_rows) is meant.
+#pragma once
+
+#include <functional>
+#include <vector>
+
+#include "mm_geom.hpp"
+
+namespace mm {
+
+// The MM_* tuning variables (include/mpimodel.h lists them), parsed by read_knobs alone.
+struct Knobs {
+    bool graphs_ok = true;      // MM_GRAPH=0 runs steps eagerly
+    long long graph_min = 16;   // steps a replayed graph holds at least (MM_GRAPH_MIN_STEPS)
+    long long graph_max = 128;  // step kernels a graph holds at most (MM_GRAPH_MAX_LAUNCHES)
+    int th = 8;                 // rows per wave, one-step kernel (MM_ROWS_PER_WAVE: 8, 16, 32)
+    bool passk = true;       // mm_passk_kernel for one-pass programs (MM_PASSK=0: one step per pass)
+    int wide = -1;           // mm_wide_kernel for one-diffusion programs where K allows
+                             // (MM_WIDE=0/1; -1 auto: slabs of >= kWideCells cells)
+    int kpass = 0;           // steps per pass, one attribute (MM_STEPS_PER_PASS, 1..kMaxSteps,
+                             // with MM_WIDE also the wide kernel's K; 0: auto)
+    int kpass_multi = 2;     // steps per pass, several attributes (MM_STEPS_PER_PASS, 1..2)
+    bool plan = true;        // pass-length planner (MM_PASS_PLAN=0: balanced passes of K)
+    double seg_waves = 0.0;  // segment waves per resident wave slot (MM_SEG_WAVES; 0: auto)
+    double seg_edge = 0.0;   // edge-strip segment length / interior length (MM_SEG_EDGE; 0: auto)
+    bool border_segments = true;  // wide split passes: full-length border segments (MM_BORDER_SEGMENTS)
+    int xcd = 0;             // XCD-contiguous block order (MM_XCD_REMAP, mm_passk_kernel)
+    bool ring_ok = true;     // the ring instance for C5-shaped chains (MM_CHAIN_RING=0: off)
+    bool sync_spin = true;   // mm_synchronize polls its streams before the blocking wait
+                             // (MM_SYNC_SPIN=0: the blocking wait alone)
+    bool self_halo = false;  // MM_SELF_HALO: one RCCL rank exchanges border rows with itself
+    int variant = -1;        // kernel tuning variant (MM_KERNEL_VARIANT; -1: by buffer size)
+};
+// `get` is std::getenv or a stand-in for it.
+Knobs read_knobs(const std::function<const char*(const char*)>& get);
+
+enum Kernel { kOneStep = 0, kPassK = 2, kWide = 3 };  // mm_info.kernel's numbers
+
+struct PlanIn {
+    long long H = 0, W = 0, h = 0, x_init = 0;
+    int nranks = 1;
+    long long min_rows = 0;  // thinnest slab of the chain: bounds the halo depth
+    long long pitch = 0;
+    int n_attr = 1;
+    bool split = false;      // interior / border split (RCCL or host halo)
+    // the program's shape: passes per step and, of a one-pass program, what its pass holds
+    int n_passes = 0;
+    int diffuse_mask = 0;
+    bool chains = false;     // pre- or post-chain transfers
+    bool ring = false;       // the ring instance runs its K = 8 passes (waves per workgroup)
+    Knobs knobs;
+    int ncu = 0;             // compute units of the device
+    // resident wave (kPassK) or workgroup (kWide) slots per CU of the instance that runs a
+    // pass of k steps, with the step sums or without: the one plan input the device gives
+    std::function<int(Kernel, int k, bool red)> slots;
+};
+
+struct KernelChoice {
+    Kernel kernel;
+    int cols;          // columns per lane
+    long long strips;  // column strips of a pass (kOneStep: 0, mm_pass_kernel's own)
+};
+
+struct Segments {
+    int th, th_edge;   // rows per interior-strip and per edge-strip segment
+    long long count;   // waves (kPassK) or workgroups (kWide)
+};
+
+// One kernel launch: rows [lo, hi) and [lo2, hi2) of the slab, as mm::PassArgs wants them.
+struct Launch {
+    long long lo = 0, hi = 0, lo2 = 0, hi2 = 0;
+    int seg = 0, th = 0, th_edge = 0, xcd_remap = 0, nstrips = 0;
+    long long waves_a = 0, waves_total = 0, partial_base = 0;
+};
+
+// One pass: the interior launch on the compute stream and, when split, the border launch
+// (the rows that read exchanged ghost rows) on the comm stream.
+struct PassLaunches {
+    KernelChoice kern;
+    int depth;        // halo rows the pass reads on each side
+    bool split;
+    Launch interior, border;
+    long long total;  // partials units of the whole pass
+};
+
+// Can the program run on the K-step kernels? One pass per step (one attribute: a single
+// diffusion; several: diffusions and transfer chains) and buffer offsets below 2^31.
+bool passk_ok(const PlanIn& in);
+KernelChoice kernel_for(const PlanIn& in, int k);
+// Steps one kernel pass advances: K with the K-step kernels, 1 otherwise. Also the ghost
+// rows one exchange must fill.
+int steps_per_launch(const PlanIn& in);
+int next_pass_len(const PlanIn& in, long long n);
+std::vector<int> pass_lengths(const PlanIn& in, long long n);
+long long seg_wave_count(long long n, long long ns, long long r, long long re);
+// Segment plan of n rows over ns strips with `slots` resident slots per CU.
+Segments segments(const PlanIn& in, Kernel kernel, int k, int slots, long long n, long long ns);
+Segments segments(const PlanIn& in, int k, bool red, long long lo, long long hi);
+PassLaunches pass_launches(const PlanIn& in, int k, bool red);
+// What mm_engine_info reports: the whole-slab plan of one pass of steps_per_launch steps,
+// in waves (a wide workgroup: wide_waves_per_block waves).
+struct SlabPlan {
+    Kernel kernel;
+    int steps_per_launch, rows_per_wave;
+    long long waves_per_pass;
+    int seg_waves_per_cu;
+};
+SlabPlan slab_plan(const PlanIn& in);
+long long graph_per(const PlanIn& in, long long nsteps, long long reduce_every, bool any = false);
+// Doubles of the partials buffer: room for every pass_launches(k, red).total.
+long long partials_need(const PlanIn& in);
+int kernel_variant(const PlanIn& in);
+
+}  // namespace mm

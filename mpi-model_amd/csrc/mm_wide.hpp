@@ -67,7 +67,6 @@ MM_WIDE_DECL(12)
 MM_WIDE_DECL(16)
 MM_WIDE_DECL(20)
 #undef MM_WIDE_DECL
-int wide_waves_k20();  // waves per workgroup of the K = 20 instance
 // four attributes, 2 columns per lane. K = 4 (mm_widea_k4.hip): any pass.
 hipError_t widea_launch_k4(int na, bool red, const PassArgs& a, hipStream_t s, int v);
 int widea_blocks_k4(int na, bool red, int nt);
@@ -89,7 +88,6 @@ MM_WIDEA8_DECL(4, 1)
 // four attributes whose pre-chain is the ring t -> t+1 mod 4 (mm_widear_k*.hip)
 hipError_t widear_launch_k8(int na, bool red, const PassArgs& a, hipStream_t s, int v);
 int widear_blocks_k8(int na, bool red, int nt);
-int widear_waves_k8();
 
 namespace {
 

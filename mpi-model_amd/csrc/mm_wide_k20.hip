@@ -56,7 +56,7 @@ int wide_blocks_k20(bool red, int nt) {
     return nt ? wide_blocks_k20_r0_n1() : wide_blocks_k20_r0_n0();
 }
 
-int wide_waves_k20() { return MM_K20_P; }
+static_assert(MM_K20_P == kWide20Waves, "mm_geom.hpp: waves per workgroup of the K = 20 instance");
 
 #endif
 

@@ -34,7 +34,7 @@ hipError_t widear_launch_k8(int na, bool red, const PassArgs& a, hipStream_t s, 
     return hipErrorInvalidValue;
 }
 
-int widear_waves_k8() { return 8 / MM_WIDEAR_KW; }
+static_assert(8 / MM_WIDEAR_KW == kWideRingWaves, "mm_geom.hpp: waves per workgroup of the ring instance");
 
 int widear_blocks_k8(int na, bool red, int nt) {
     return na == 4 ? wide_blocks<2, 4, MM_WIDEAR_KW, 8 / MM_WIDEAR_KW, 2>(red, nt) : 0;

@@ -103,6 +103,10 @@ def check_deep_chain(gpu, O, monkeypatch, H, W, G, k, wide, extra=None):
 @pytest.mark.parametrize("reduce_every", [1, 3])
 @pytest.mark.parametrize("H,W,G", [(100, 488, 3), (41, 200, 8), (300, 700, 2), (130, 257, 4)])
 def test_deep_halo_chain_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, env):
+    check_chain_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, env)
+
+
+def check_chain_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, env):
     # per-step sums of every slab (partials at partial_base offsets: interior segments
     # first, then the border blocks) summed over the slabs in rank order
     steps = 2 * env["MM_STEPS_PER_PASS"] + 1 if "MM_STEPS_PER_PASS" in env else 9
@@ -130,6 +134,29 @@ def test_deep_halo_chain_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, e
         tot = tot + hst[:, 0]
     for a, b in zip(tot, want):
         assert abs(a - b) <= 1e-12 * b
+
+
+# Slabs of 26 and 27 rows under the level-split kernel: the whole-slab segment length is
+# never below 16, so the full-length border segments are T = h / 2 = 13 rows -- an odd
+# border segment whose bottom half starts on an odd row, beside an empty interior launch
+# (h = 26) or a one-row interior (h = 27). MM_BORDER_SEGMENTS=0: K-row borders there.
+THIN_CHAINS = [(52, 300, 2), (54, 260, 2)]
+
+
+@pytest.mark.parametrize("bseg", [0, 1])
+@pytest.mark.parametrize("k", [4, 8])
+@pytest.mark.parametrize("H,W,G", THIN_CHAINS)
+def test_thin_slab_border_segments_bit_exact(gpu, O, monkeypatch, H, W, G, k, bseg):
+    check_deep_chain(gpu, O, monkeypatch, H, W, G, k, 1, extra={"MM_BORDER_SEGMENTS": bseg})
+
+
+@pytest.mark.parametrize("bseg", [0, 1])
+@pytest.mark.parametrize("k", [4, 8])
+@pytest.mark.parametrize("reduce_every", [1, 3])
+@pytest.mark.parametrize("H,W,G", THIN_CHAINS)
+def test_thin_slab_border_segments_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, k, bseg):
+    env = {"MM_WIDE": 1, "MM_STEPS_PER_PASS": k, "MM_BORDER_SEGMENTS": bseg}
+    check_chain_step_sums(gpu, O, monkeypatch, H, W, G, reduce_every, env)
 
 
 C5_FLOWS = [(2, 0, 1, 0.05), (2, 1, 2, 0.03), (2, 2, 3, 0.02), (2, 3, 0, 0.01),
