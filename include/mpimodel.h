@@ -49,7 +49,25 @@ enum mm_flow_kind {
     MM_FLOW_DIFFUSE = 1,
     /* Exponencial from attribute a to attribute b of the SAME cell:
      * out = rate*v_a; v_a -= out; v_b += out (b < 0: outflow leaves the system). */
-    MM_FLOW_TRANSFER = 2
+    MM_FLOW_TRANSFER = 2,
+    /* Exponencial from every cell of attribute a to its Moore neighbours with a per-cell
+     * rate: the attribute's rate field f (mm_rate_field_upload / mm_rate_field_fill). The
+     * reference's per-emitter update (src/Model.hpp:199,206-211,234) applied to every
+     * cell. For the in-grid cell c = (x, y) with cnt(c) in-grid Moore neighbours:
+     *   out(c) = f(c) * v(c)              if cnt(c) > 0, else 0
+     *   s(c)   = out(c) * 0.125           if cnt(c) == 8
+     *            out(c) / (double)cnt(c)  otherwise     (0 for any cell outside the grid)
+     *   q(x,y) = s(x-1,y) + s(x+1,y)
+     *   t(x,y) = q(x,y) + s(x,y)
+     *   nb     = (t(x,y-1) + t(x,y+1)) + q(x,y)
+     *   v'(c)  = (v(c) - out(c)) + nb
+     * every operation a separate IEEE fp64 one (no fused multiply-add, the IEEE division):
+     * bit for bit or_field_step_general of oracle/mm_oracle.c with outf = f * v. A field
+     * that is zero except at chosen cells is a multi-source flow, a constant field the
+     * whole-grid flow, a 0/1-scaled field a mask. mm_add_flow ignores b and rate for this
+     * kind. Field diffusions run one step per kernel pass in passes of their own
+     * (consecutive ones of distinct attributes share a pass). */
+    MM_FLOW_DIFFUSE_FIELD = 3
 };
 
 enum mm_fill_mode {
@@ -89,7 +107,8 @@ typedef struct mm_info {
     int steps_per_launch;      /* steps fused per kernel pass (temporal blocking): 1..10
                                   (mm_passk_kernel), 4/8/12/16/20 (mm_wide_kernel, 4/8 for
                                   four-attribute programs); mixed plans: mm_pass_plan */
-    int kernel;                /* step kernel: 0 mm_pass_kernel (one step per pass),
+    int kernel;                /* step kernel: 0 one step per pass (mm_pass_kernel, or
+                                  mm_field_kernel for a rate-field pass),
                                   2 mm_passk_kernel (steps_per_launch steps per pass, all
                                   levels in one wave), 3 mm_wide_kernel (steps_per_launch
                                   steps per pass, the levels split over 4 waves) */
@@ -226,6 +245,21 @@ int mm_download(mm_engine* eng, int attr, double* host);
 int mm_clear_flows(mm_engine* eng);
 int mm_add_flow(mm_engine* eng, int kind, int a, int b, double rate);
 
+/* The rate field of attribute attr (MM_FLOW_DIFFUSE_FIELD): one static (h + 2*kGhost) x
+ * pitch fp64 buffer, allocated and zeroed on first use (counted in mm_info.bytes_device;
+ * allocating it drops the cached graphs). mm_rate_field_upload copies nrows rows of W
+ * doubles starting at LOCAL row row0 (as mm_debug_read_rows: -kGhost <= row0, row0 + nrows
+ * <= h + kGhost); rows outside the global grid are skipped, rows never uploaded are 0. In
+ * a chain the caller supplies at least one ghost row on each side that has a neighbour:
+ * the field is static, so the engine never exchanges it (MM_HALO_HOST and MM_HALO_RCCL
+ * alike). Non-finite values, a bad range or a bad attr return MM_ERR_INVALID.
+ * mm_rate_field_fill sets every in-grid row, ghost rows included, to value on the device.
+ * Both are synchronous, like mm_upload, and do not reset steps_done. mm_run / mm_prepare of
+ * a program with a field diffusion whose attribute has no field return MM_ERR_STATE. */
+int mm_rate_field_upload(mm_engine* eng, int attr, long long row0, long long nrows,
+                         const double* host);
+int mm_rate_field_fill(mm_engine* eng, int attr, double value);
+
 /* src/Model.hpp:176-235 -- the reference's single-source Exponencial application:
  * out = rate*captured (src/Exponencial.hpp:14-16, the Flow's own copy of the
  * source value), share = out/count_neighbors to every in-grid Moore neighbour,
@@ -299,7 +333,8 @@ int mm_debug_fill_padding(mm_engine* eng, double value);
  * step-kernel launch on the stream it is launched on; mm_timing returns the
  * number of timed launches, their summed duration (ms) and the average algorithmic
  * bytes one launch moves: 16 B per cell of its rows per attribute (read once, written
- * once), whether the launch advances one step or K. */
+ * once), whether the launch advances one step or K; 24 B for an attribute
+ * that diffuses by its rate field in that pass (the field is read too). */
 int mm_set_timing(mm_engine* eng, int on);
 int mm_timing(mm_engine* eng, long long* n_launches, double* total_ms, double* bytes_per_launch);
 

@@ -30,6 +30,13 @@ public:
         check(mm_fill(e_, attr, MM_FILL_RANDOM, 0.0, seed));
     }
     void add_flow(int kind, int a, int b, double rate) { check(mm_add_flow(e_, kind, a, b, rate)); }
+    // diffusion of attr by its per-cell rate field (MM_FLOW_DIFFUSE_FIELD)
+    void add_diffuse_field(int attr) { check(mm_add_flow(e_, MM_FLOW_DIFFUSE_FIELD, attr, attr, 0.0)); }
+    // nrows rows of W rates from local row row0 (ghost rows included) / one rate everywhere
+    void rate_field_upload(int attr, long long row0, long long nrows, const double* host) {
+        check(mm_rate_field_upload(e_, attr, row0, nrows, host));
+    }
+    void rate_field_fill(int attr, double value) { check(mm_rate_field_fill(e_, attr, value)); }
     void point_apply(int attr, long long sx, long long sy, double captured, double rate) {
         check(mm_point_apply(e_, attr, sx, sy, captured, rate));
     }

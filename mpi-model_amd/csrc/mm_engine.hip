@@ -5,7 +5,8 @@
 //     ping-pong) with kGhost ghost rows above and below, pitch a multiple of 128;
 //   * a one-pass flow program runs K steps per kernel pass (mm_passk_kernel, temporal
 //     blocking: 16/K B of HBM traffic per cell-update); other programs run one step
-//     per pass (mm_pass_kernel);
+//     per pass (mm_pass_kernel; mm_field_kernel for a rate-field pass, whose per-cell rate
+//     map is one more static buffer of the same shape per attribute);
 //   * a compute stream and a comm stream; with a halo (RCCL or host transport) each pass
 //     runs the interior rows on the compute stream while the `depth` border rows wait
 //     for the exchange on the comm stream (RCCL: ncclSend/ncclRecv of `depth` rows to
@@ -68,11 +69,13 @@ struct Transfer {
     double rate;
 };
 
-// A fused pass: pre-chain transfers, at most one diffusion per attribute, post-chain.
+// A fused pass: pre-chain transfers, at most one diffusion per attribute, post-chain. A
+// rate-field pass (field_mask != 0) holds field diffusions of distinct attributes only.
 struct Pass {
     std::vector<Transfer> pre, post;
     int diffuse_mask = 0;
     double drate[mm::kMaxAttr] = {0, 0, 0, 0};
+    int field_mask = 0;
 };
 
 struct FlowDesc {
@@ -91,6 +94,10 @@ struct mm_engine {
     size_t bytes = 0;
     double* buf[2][mm::kMaxAttr] = {};
     int cur = 0;
+    // static rate fields (MM_FLOW_DIFFUSE_FIELD): one (h + 2*kGhost) x pitch buffer per
+    // attribute that has one, allocated and zeroed on first use; fld points at owned row 0
+    double* fld_base[mm::kMaxAttr] = {};
+    double* fld[mm::kMaxAttr] = {};
     hipStream_t s_comp = nullptr, s_comm = nullptr;
     hipEvent_t ev_ready = nullptr, ev_halo = nullptr;
     hipEvent_t ev_comp_mark = nullptr, ev_comm_done = nullptr;
@@ -152,7 +159,20 @@ int compile_passes(mm_engine* e) {
     Pass cur;
     bool open = false;
     for (const FlowDesc& f : e->flows) {
-        if (f.kind == MM_FLOW_TRANSFER) {
+        // rate-field diffusions get passes of their own: consecutive ones of distinct
+        // attributes share a pass; any other flow closes it, and they close any other pass
+        const bool fieldf = f.kind == MM_FLOW_DIFFUSE_FIELD;
+        if (open && (fieldf ? (!cur.field_mask || (cur.field_mask & (1 << f.a))) : cur.field_mask != 0)) {
+            e->passes.push_back(cur);
+            open = false;
+        }
+        if (fieldf) {
+            if (!open) {
+                cur = Pass();
+                open = true;
+            }
+            cur.field_mask |= 1 << f.a;
+        } else if (f.kind == MM_FLOW_TRANSFER) {
             if (!open) {
                 cur = Pass();
                 open = true;
@@ -207,6 +227,8 @@ void fill_args(const mm_engine* e, const Pass& p, mm::PassArgs& A) {
         A.post_r[i] = p.post[i].rate;
     }
     A.partials = e->partials;
+    A.field_mask = p.field_mask;
+    for (int a = 0; a < e->na; ++a) A.field[a] = ((p.field_mask >> a) & 1) ? e->fld[a] : nullptr;
 }
 
 hipEvent_t next_event(mm_engine* e) {
@@ -294,6 +316,8 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     pin.diffuse_mask = p ? p->diffuse_mask : 0;
     pin.chains = p && !(p->pre.empty() && p->post.empty());
     pin.ring = wring(e) != 0;
+    pin.field = false;
+    for (const Pass& q : e->passes) pin.field = pin.field || q.field_mask != 0;
 }
 
 // Border-row exchange with both neighbours in one RCCL group: the first / last `depth`
@@ -382,6 +406,8 @@ int launch(mm_engine* e, const mm::PassLaunches& pl, bool red, const mm::PassArg
         MM_HIP(mm::launch_wide(k, pl.kern.cols, e->na, red, A, s, (nt & 1) | wvar(e)));
     else if (pl.kern.kernel == mm::kPassK)
         MM_HIP(mm::launch_passk(k, e->na, red, A, s, nt));
+    else if (A.field_mask)  // a rate-field pass
+        MM_HIP(mm::launch_field(e->na, red, A, s, nt));
     else
         MM_HIP(mm::launch_pass(e->na, red, A, s, e->variant));
     return MM_OK;
@@ -431,7 +457,9 @@ int enqueue_pass(mm_engine* e, const Pass& p, int k, int mask, bool time_it, boo
         t1 = next_event(e);
         if (!t0 || !t1) return fail(MM_ERR_HIP, "hipEventCreate failed");
         e->ev_bytes.resize(e->ev_used / 2);
-        e->ev_bytes.back() = 16.0 * (double)(pl.interior.hi - pl.interior.lo) * (double)e->d.W * e->na;
+        // a rate-field attribute also reads its field: 24 B per cell
+        e->ev_bytes.back() = (16.0 * e->na + 8.0 * __builtin_popcount((unsigned)p.field_mask)) *
+                             (double)(pl.interior.hi - pl.interior.lo) * (double)e->d.W;
         MM_HIP(hipEventRecord(t0, e->s_comp));
     }
     MM_TRY(launch(e, pl, red, A, e->s_comp, false));
@@ -806,6 +834,8 @@ int mm_engine_destroy(mm_engine* e) {
     if (e->s_comp) (void)hipStreamDestroy(e->s_comp);
     if (e->s_comm) (void)hipStreamDestroy(e->s_comm);
     if (e->base) (void)hipFree(e->base);
+    for (double* f : e->fld_base)
+        if (f) (void)hipFree(f);
     if (e->partials) (void)hipFree(e->partials);
     if (e->hist) (void)hipFree(e->hist);
     if (e->hist_n) (void)hipFree(e->hist_n);
@@ -885,22 +915,87 @@ int mm_clear_flows(mm_engine* e) {
 
 int mm_add_flow(mm_engine* e, int kind, int a, int b, double rate) {
     if (!e) return fail(MM_ERR_INVALID, "mm_add_flow: null");
-    if (kind != MM_FLOW_DIFFUSE && kind != MM_FLOW_TRANSFER)
+    if (kind != MM_FLOW_DIFFUSE && kind != MM_FLOW_TRANSFER && kind != MM_FLOW_DIFFUSE_FIELD)
         return fail(MM_ERR_INVALID, "mm_add_flow: unknown flow kind");
     if (a < 0 || a >= e->na) return fail(MM_ERR_INVALID, "mm_add_flow: attribute out of range");
     if (kind == MM_FLOW_TRANSFER && b >= e->na)
         return fail(MM_ERR_INVALID, "mm_add_flow: target attribute out of range");
+    if (kind == MM_FLOW_DIFFUSE_FIELD) rate = 0.0;  // the rate is the attribute's field
     if (!std::isfinite(rate)) return fail(MM_ERR_INVALID, "mm_add_flow: rate must be finite");
     MM_TRY(set_device(e));
     MM_HIP(hipStreamSynchronize(e->s_comp));
     e->flows.push_back({kind, a, kind == MM_FLOW_TRANSFER ? (b < 0 ? -1 : b) : a, rate});
     drop_graphs(e);
     MM_TRY(compile_passes(e));
-    // transfers or several attributes: the generic kernel exists for 8-row blocks only
+    // transfers, several attributes or a rate field: those kernels exist for 8-row blocks only
     bool chains = e->na > 1;
-    for (const Pass& p : e->passes) chains = chains || !p.pre.empty() || !p.post.empty();
+    for (const Pass& p : e->passes)
+        chains = chains || !p.pre.empty() || !p.post.empty() || p.field_mask != 0;
     if (chains) e->pin.knobs.th = 8;
     sync_program(e);
+    return MM_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The rate field of one attribute, allocated and zeroed on first use. The step graphs
+// capture the field pointers, so a new field drops them.
+int ensure_field(mm_engine* e, int attr) {
+    if (e->fld[attr]) return MM_OK;
+    const size_t n = sizeof(double) * (size_t)e->rows_alloc * (size_t)e->pitch;
+    double* p = nullptr;
+    if (hipMalloc(&p, n) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MM_ERR_NOMEM, "rate field allocation failed");
+    }
+    e->fld_base[attr] = p;
+    e->fld[attr] = p + mm::kGhost * e->pitch;
+    e->bytes += n;
+    MM_HIP(hipMemsetAsync(p, 0, n, e->s_comp));
+    MM_HIP(hipStreamSynchronize(e->s_comp));
+    drop_graphs(e);
+    return MM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mm_rate_field_upload(mm_engine* e, int attr, long long row0, long long nrows,
+                         const double* host) {
+    if (!e || !host || attr < 0 || attr >= e->na || nrows < 0 || row0 < -mm::kGhost ||
+        row0 + nrows > e->d.h + mm::kGhost)
+        return fail(MM_ERR_INVALID, "mm_rate_field_upload: bad attribute, or rows outside the "
+                                    "slab + ghost rows");
+    const long long W = e->d.W;
+    for (long long i = 0; i < nrows * W; ++i)
+        if (!std::isfinite(host[i]))
+            return fail(MM_ERR_INVALID, "mm_rate_field_upload: rates must be finite");
+    MM_TRY(set_device(e));
+    MM_TRY(ensure_field(e, attr));
+    // rows outside the global grid are skipped
+    const long long lo = std::max(row0, -e->d.x_init);
+    const long long hi = std::min(row0 + nrows, e->d.H - e->d.x_init);
+    if (hi <= lo) return MM_OK;
+    // the running steps read the field: on the compute stream (every run ends there), or on
+    // the comm stream behind an event the compute stream waits for
+    MM_HIP(hipMemcpy2DAsync(e->fld[attr] + lo * e->pitch, sizeof(double) * e->pitch,
+                            host + (lo - row0) * W, sizeof(double) * W, sizeof(double) * W,
+                            (size_t)(hi - lo), hipMemcpyHostToDevice, e->s_comp));
+    MM_HIP(hipStreamSynchronize(e->s_comp));
+    return MM_OK;
+}
+
+int mm_rate_field_fill(mm_engine* e, int attr, double value) {
+    if (!e || attr < 0 || attr >= e->na || !std::isfinite(value))
+        return fail(MM_ERR_INVALID, "mm_rate_field_fill: bad attribute or non-finite rate");
+    MM_TRY(set_device(e));
+    MM_TRY(ensure_field(e, attr));
+    MM_HIP(mm::launch_fill(e->fld[attr], e->pitch, e->d.H, e->d.W, e->d.x_init, e->d.h,
+                           MM_FILL_UNIFORM, value, 0, e->s_comp));
+    MM_HIP(hipStreamSynchronize(e->s_comp));
     return MM_OK;
 }
 
@@ -935,6 +1030,11 @@ int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char
     if (!e || nsteps < 0 || reduce_every < 0) return fail(MM_ERR_INVALID, std::string(who) + ": bad arguments");
     if (nsteps == 0) return MM_OK;
     if (e->passes.empty()) return fail(MM_ERR_STATE, std::string(who) + ": no flow added (mm_add_flow)");
+    for (const Pass& p : e->passes)
+        for (int a = 0; a < e->na; ++a)
+            if (((p.field_mask >> a) & 1) && !e->fld[a])
+                return fail(MM_ERR_STATE, std::string(who) + ": a rate-field diffusion's attribute has "
+                                          "no field (mm_rate_field_upload / mm_rate_field_fill)");
     if (e->d.halo_mode == MM_HALO_HOST && e->d.nranks > 1) {
         if (e->passes.size() != 1)
             return fail(MM_ERR_STATE, std::string(who) + ": the host halo transport runs one-pass flow programs only");
@@ -1192,6 +1292,11 @@ int mm_debug_fill_padding(mm_engine* e, double value) {
                                     sizeof(double) * e->pitch, src.data(), sizeof(double) * pad,
                                     sizeof(double) * pad, e->rows_alloc, hipMemcpyHostToDevice,
                                     e->s_comp));
+    for (int a = 0; a < e->na; ++a)
+        if (e->fld_base[a])
+            MM_HIP(hipMemcpy2DAsync(e->fld_base[a] + e->d.W, sizeof(double) * e->pitch, src.data(),
+                                    sizeof(double) * pad, sizeof(double) * pad, e->rows_alloc,
+                                    hipMemcpyHostToDevice, e->s_comp));
     MM_HIP(hipStreamSynchronize(e->s_comp));
     return MM_OK;
 }

@@ -35,10 +35,18 @@ struct PassArgs {
     int xcd_remap;          // mm_passk_kernel: XCD-contiguous block order (grid padded to 8)
     int seg;                // mm_passk_kernel: segment schedule (th / th_edge rows per wave)
     int th_edge;            // mm_passk_kernel segments: rows per wave of the two edge strips
+    const double* field[kMaxAttr];  // mm_field_kernel: rate field of attribute a (row 0, same
+                                    // pitch and ghost rows as the attribute buffers)
+    int field_mask;         // bit a: attribute a diffuses by field[a] in this pass
 };
 
 // Launchers (mm_kernels.hip). All enqueue on `s` and return the launch status.
 hipError_t launch_pass(int na, bool reduce, const PassArgs& a, hipStream_t s, int variant);
+// One step of a rate-field pass (mm_field_kernel, mm_field.hip): the attributes of
+// a.field_mask diffuse by their per-cell rate a.field[], the others are copied through. Row
+// ranges, wave mapping and partials as launch_pass; a.th 8, or 1 (border rows). variant bit
+// 0: non-temporal stores (one attribute).
+hipError_t launch_field(int na, bool reduce, const PassArgs& a, hipStream_t s, int variant);
 // K fused steps of a one-pass flow program (NA = 1: K 1..10, one diffusion; NA 2..4:
 // K 1..2, diffusions and transfer chains) on overlapped strips (mm_passk_kernel,
 // mm_kernels_k.hip). a.seg: segment schedule, a.th / a.th_edge rows per wave; else 4-row

@@ -217,7 +217,7 @@ long long waves_for(long long nstrips, long long n, int th) { return n <= 0 ? 0 
 }  // namespace
 
 bool passk_ok(const PlanIn& in) {
-    if (!in.knobs.passk || in.n_passes != 1) return false;
+    if (!in.knobs.passk || in.n_passes != 1 || in.field) return false;
     if (passk_max_rows(kMaxSteps, in.pitch) < 64) return false;
     if (in.n_attr == 1) return in.diffuse_mask == 1 && !in.chains;
     return true;

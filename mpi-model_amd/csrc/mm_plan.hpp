@@ -54,6 +54,7 @@ struct PlanIn {
     int diffuse_mask = 0;
     bool chains = false;     // pre- or post-chain transfers
     bool ring = false;       // the ring instance runs its K = 8 passes (waves per workgroup)
+    bool field = false;      // some pass is a rate-field pass (mm_field_kernel): one step per pass
     Knobs knobs;
     int ncu = 0;             // compute units of the device
     // resident wave (kPassK) or workgroup (kWide) slots per CU of the instance that runs a
@@ -90,7 +91,8 @@ struct PassLaunches {
 };
 
 // Can the program run on the K-step kernels? One pass per step (one attribute: a single
-// diffusion; several: diffusions and transfer chains) and buffer offsets below 2^31.
+// diffusion; several: diffusions and transfer chains), no rate-field pass, and buffer offsets
+// below 2^31.
 bool passk_ok(const PlanIn& in);
 KernelChoice kernel_for(const PlanIn& in, int k);
 // Steps one kernel pass advances: K with the K-step kernels, 1 otherwise. Also the ghost

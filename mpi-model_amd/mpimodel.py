@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("MM_LIB_PATH") or os.path.join(HERE, "libmpimodel_hip.
 MM_OK = 0
 MM_FLOW_DIFFUSE = 1
 MM_FLOW_TRANSFER = 2
+MM_FLOW_DIFFUSE_FIELD = 3
 MM_FILL_UNIFORM = 0
 MM_FILL_RANDOM = 1
 MM_HALO_NONE = 0
@@ -39,6 +40,7 @@ EXPORTS = [
     "mm_set_timing", "mm_timing", "mm_partition_rect_reference", "mm_owner_rect_reference",
     "mm_wire_format_partition", "mm_wire_format_flow", "mm_wire_parse_partition",
     "mm_wire_parse_flow", "mm_point_strict_applies", "mm_point_apply_strict",
+    "mm_rate_field_upload", "mm_rate_field_fill",
 ]
 
 WIRE_LEN = 23
@@ -129,6 +131,8 @@ def lib():
             "mm_wire_parse_flow": (I, [ctypes.c_char_p, I, pI, pI, pI, pI,
                                        ctypes.POINTER(D)]),
             "mm_timing": (I, [P, pLL, ctypes.POINTER(D), ctypes.POINTER(D)]),
+            "mm_rate_field_upload": (I, [P, I, LL, LL, P]),
+            "mm_rate_field_fill": (I, [P, I, D]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -313,6 +317,22 @@ class Engine:
 
     def add_transfer(self, a, b, rate):
         check(lib().mm_add_flow(self.ptr, MM_FLOW_TRANSFER, a, b, rate))
+
+    def add_diffuse_field(self, attr):
+        """Diffusion of `attr` by its per-cell rate field (rate_field_upload / rate_field_fill)."""
+        check(lib().mm_add_flow(self.ptr, MM_FLOW_DIFFUSE_FIELD, attr, attr, 0.0))
+
+    def rate_field_upload(self, host, attr=0, row0=0):
+        """Rows row0.. (local; ghost rows -20..-1 and h..h+19 included) of attr's rate field
+        from a 2-D array of W columns. Rows never uploaded are 0; a slab of a chain uploads
+        its rows -1..h (clipped to the grid), the engine never exchanges the field."""
+        a = np.ascontiguousarray(host, dtype=np.float64)
+        assert a.ndim == 2 and a.shape[1] == self.W
+        check(lib().mm_rate_field_upload(self.ptr, attr, row0, a.shape[0], _dptr(a)))
+
+    def rate_field_fill(self, value, attr=0):
+        """Every in-grid row of attr's rate field, ghost rows included, set to value."""
+        check(lib().mm_rate_field_fill(self.ptr, attr, float(value)))
 
     def point_apply(self, sx, sy, captured, rate, attr=0):
         check(lib().mm_point_apply(self.ptr, attr, sx, sy, captured, rate))
