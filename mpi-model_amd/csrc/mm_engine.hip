@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "../../include/mpimodel.h"
-#include "mm_internal.hpp"
+#include "mm_inst.hpp"
 #include "mm_plan.hpp"
 
 namespace {
@@ -61,8 +61,6 @@ int fail(int code, const std::string& msg) {
         int rc_ = (expr);        \
         if (rc_ != MM_OK) return rc_; \
     } while (0)
-
-long long span_rows(long long n, long long i) { return (i >= 0 && i < n) ? 1 + (i > 0) + (i < n - 1) : 0; }
 
 struct Transfer {
     int a, b;
@@ -109,7 +107,7 @@ struct mm_engine {
 
     mm::PlanIn pin;  // what the planner sees of the engine (mm_plan.hpp): slab, program shape,
                      // the MM_* knobs, the device; pin.split: interior / border split
-    std::map<long long, int> slots;  // occupancy cache (slots_per_cu)
+    std::map<const mm::KernelInst*, int> slots;  // occupancy cache (slots_per_cu)
     bool self_halo = false;  // test mode: one RCCL rank exchanges border rows with itself
     int variant = 0;  // kernel tuning variant (MM_KERNEL_VARIANT), 0 = default
     double* partials = nullptr;
@@ -240,24 +238,36 @@ hipEvent_t next_event(mm_engine* e) {
     return e->ev_pool[e->ev_used++];
 }
 
-// Variant bit 1 of a wide launch: a one-pass program of four attributes whose pre-chain
-// is the ring of transfers t -> t+1 mod 4 in that order, without a post-chain (config C5's
-// topology), runs the instance with the chain's operands fixed at compile time.
-int wring(const mm_engine* e) {
-    if (!e->pin.knobs.ring_ok || e->na != 4 || e->passes.size() != 1) return 0;
+// A one-pass program of four attributes whose pre-chain is the ring of transfers t -> t+1
+// mod 4 in that order, without a post-chain (config C5's topology), runs the wide instance
+// with the chain's operands fixed at compile time.
+bool wring(const mm_engine* e) {
+    if (!e->pin.knobs.ring_ok || e->na != 4 || e->passes.size() != 1) return false;
     const Pass& p = e->passes[0];
-    if ((int)p.pre.size() != e->na || !p.post.empty() || p.diffuse_mask != 15) return 0;
+    if ((int)p.pre.size() != e->na || !p.post.empty() || p.diffuse_mask != 15) return false;
     for (int t = 0; t < e->na; ++t)
-        if (p.pre[t].a != t || p.pre[t].b != (t + 1) % e->na) return 0;
-    return 2;
+        if (p.pre[t].a != t || p.pre[t].b != (t + 1) % e->na) return false;
+    return true;
 }
 
-// Variant bits of a wide launch beyond bit 0 (mm_internal.hpp): the ring instance (2), a
-// post-chain (4), the number of diffusing attributes (bits 4-6; relabel puts them first).
-int wvar(const mm_engine* e) {
-    if (e->na == 1 || e->passes.size() != 1) return 0;
-    const Pass& p = e->passes[0];
-    return wring(e) | (p.post.empty() ? 0 : 4) | (__builtin_popcount((unsigned)p.diffuse_mask) << 4);
+// The key of the instance that runs a k-step pass of the engine's program (mm_inst.hpp).
+// nt: non-temporal stores -- bit 0 of the tuning variant and no other bit of it, so no user
+// value of MM_KERNEL_VARIANT selects the ring instance. A four-attribute wide pass adds what
+// its instance has at compile time: the ring, a post-chain, the diffusing attributes
+// (relabel puts them first).
+mm::InstKey inst_key(const mm_engine* e, mm::Kernel kernel, int k, int cols, bool seg, bool red,
+                     bool nt) {
+    mm::InstKey q{};
+    q.family = kernel == mm::kWide ? mm::kInstWide : mm::kInstPassK;
+    q.k = k, q.cols = cols, q.na = e->na;
+    q.seg = seg, q.red = red, q.nt = nt;
+    if (kernel == mm::kWide && e->na > 1 && e->passes.size() == 1) {
+        const Pass& p = e->passes[0];
+        q.ring = wring(e);
+        q.post = !p.post.empty();
+        q.nd = __builtin_popcount((unsigned)p.diffuse_mask);
+    }
+    return q;
 }
 
 // Identity attribute permutation, packed 2 bits per slot (launch_finalize_levels).
@@ -298,14 +308,15 @@ int relabel(const mm_engine* e, mm::PassArgs& A) {
 }
 
 // Resident slots per CU of the instance that runs a k-step pass (mm::PlanIn::slots): waves
-// of mm_passk_kernel, workgroups of mm_wide_kernel, from the occupancy API, cached.
+// of mm_passk_kernel, workgroups of mm_wide_kernel, from the instance's registers and LDS,
+// cached by instance. An unknown instance counts one slot, as a failed query does.
 int slots_per_cu(mm_engine* e, mm::Kernel kernel, int k, bool red) {
     const bool wide = kernel == mm::kWide;
-    const int nt = (e->variant & 1) | (wide ? wvar(e) : 0);
-    int& s = e->slots[((long long)nt << 9) | (wide ? 256 : 0) | (red ? 128 : 0) | k];
-    if (!s)
-        s = std::max(1, wide ? mm::wide_blocks_per_cu(k, e->na > 1 ? 2 : 4, e->na, red, nt)
-                             : mm::passk_waves_per_cu(k, e->na, red, nt));
+    const mm::KernelInst* inst = mm::find_inst(
+        inst_key(e, kernel, k, wide ? (e->na > 1 ? 2 : 4) : 2, true, red, e->variant & 1));
+    if (!inst) return 1;
+    int& s = e->slots[inst];
+    if (!s) s = std::max(1, mm::inst_blocks_per_cu(*inst) * (wide ? 1 : mm::kWavesPerBlock));
     return s;
 }
 
@@ -315,7 +326,7 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     const Pass* p = pin.n_passes == 1 ? &e->passes[0] : nullptr;
     pin.diffuse_mask = p ? p->diffuse_mask : 0;
     pin.chains = p && !(p->pre.empty() && p->post.empty());
-    pin.ring = wring(e) != 0;
+    pin.ring = wring(e);
     pin.field = false;
     for (const Pass& q : e->passes) pin.field = pin.field || q.field_mask != 0;
 }
@@ -397,15 +408,13 @@ int unsplit_halo(mm_engine* e, int depth) {
     return MM_OK;
 }
 
-// One kernel launch of a pass on a stream. A border launch takes no tuning variant (the
-// wide kernel: its instance bits alone).
+// One kernel launch of a pass on a stream. A border launch takes no tuning variant.
 int launch(mm_engine* e, const mm::PassLaunches& pl, bool red, const mm::PassArgs& A, hipStream_t s,
            bool border) {
-    const int k = pl.depth, nt = border ? 0 : e->variant;
-    if (pl.kern.kernel == mm::kWide)
-        MM_HIP(mm::launch_wide(k, pl.kern.cols, e->na, red, A, s, (nt & 1) | wvar(e)));
-    else if (pl.kern.kernel == mm::kPassK)
-        MM_HIP(mm::launch_passk(k, e->na, red, A, s, nt));
+    const int nt = border ? 0 : e->variant;
+    if (pl.kern.kernel == mm::kWide || pl.kern.kernel == mm::kPassK)
+        MM_HIP(mm::launch_kstep(
+            inst_key(e, pl.kern.kernel, pl.depth, pl.kern.cols, A.seg != 0, red, nt & 1), A, s));
     else if (A.field_mask)  // a rate-field pass
         MM_HIP(mm::launch_field(e->na, red, A, s, nt));
     else
@@ -666,7 +675,7 @@ int mm_partition_rows(long long H, int G, int g, long long* x_init, long long* h
 }
 
 int mm_neighbor_count(long long H, long long W, long long x, long long y) {
-    const long long sx = span_rows(H, x), sy = span_rows(W, y);
+    const long long sx = mm::span3(H, x), sy = mm::span3(W, y);
     return (sx && sy) ? (int)(sx * sy - 1) : 0;
 }
 

@@ -29,47 +29,12 @@
 // 24 B per cell (read v, read f, write v'): HBM-bound by a wide margin.
 // Attributes outside field_mask are copied through (the pass flips every attribute's
 // ping-pong buffers).
-#include "mm_internal.hpp"
+#include "mm_inst.hpp"
+#include "mm_lane.hpp"
 
 namespace mm {
 
 namespace {
-
-__device__ __forceinline__ double dpp_lower(double src, double old) {
-    // lane i <- lane i-1 (wave_shr:1); lane 0 keeps `old`
-    const long long s = __double_as_longlong(src), o = __double_as_longlong(old);
-    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)s, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(s >> 32), 0x138, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double dpp_upper(double src, double old) {
-    // lane i <- lane i+1 (wave_shl:1); lane 63 keeps `old`
-    const long long s = __double_as_longlong(src), o = __double_as_longlong(old);
-    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)s, 0x130, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(s >> 32), 0x130, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// 1 + (i > 0) + (i < n-1) inside [0, n), 0 outside: cnt = span(x)*span(y) - 1
-__device__ __forceinline__ int span3f(long long n, long long i) {
-    return (i >= 0 && i < n) ? 1 + (i > 0) + (i < n - 1) : 0;
-}
-
-typedef double dv2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOB = 0x80000000u;  // voffset past any num_records: loads 0, stores dropped
-
-// Buffer descriptor of local row r of one buffer; rows past rmax get num_records = 0 (their
-// loads return 0 and their stores are dropped without memory traffic).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t frow_rsrc(const double* buf, int r, int rmax,
-                                                            long long pitch) {
-    const bool ok = r <= rmax;
-    const double* p = buf + (long long)(ok ? r : 0) * pitch;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), 0,
-                                             ok ? (int)(pitch * 8) : 0, 0x00020000);
-}
 
 // One input row as this lane sees it: values and rates of its two columns and its edge column.
 template <int NA>
@@ -92,13 +57,13 @@ __device__ __forceinline__ void fload_row(const PassArgs& A, int r, int rmax, un
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         const bool dif = A.field_mask & (1 << a);  // kernel-uniform
-        const __amdgpu_buffer_rsrc_t rs = frow_rsrc(A.in[a], r, rmax, A.pitch);
+        const __amdgpu_buffer_rsrc_t rs = row_rsrc(A.in[a], r, rmax, A.pitch);
         const dv2 p = __builtin_bit_cast(dv2, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
         o.v0[a] = p.x;
         o.v1[a] = p.y;
         if (dif) {
             o.ve[a] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, eoff, 0, 0));
-            const __amdgpu_buffer_rsrc_t rf = frow_rsrc(A.field[a], r, rmax, A.pitch);
+            const __amdgpu_buffer_rsrc_t rf = row_rsrc(A.field[a], r, rmax, A.pitch);
             const dv2 q = __builtin_bit_cast(dv2, __builtin_amdgcn_raw_buffer_load_b128(rf, voff, 0, 0));
             o.f0[a] = q.x;
             o.f1[a] = q.y;
@@ -122,7 +87,7 @@ template <int NA>
 __device__ __forceinline__ void fprocess_row(const PassArgs& A, int r, const FRaw<NA>& raw,
                                              bool fast_cols, int sy0, int sy1, int sye,
                                              FRow<NA>& o) {
-    const int sx = span3f(A.H, A.x_init + r);  // wave-uniform
+    const int sx = span3(A.H, A.x_init + r);  // wave-uniform
     const bool fast = sx == 3 && fast_cols;    // cnt == 8 in all three columns
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
@@ -163,8 +128,8 @@ __device__ __forceinline__ void femit_row(const PassArgs& A, int r, int rmax, un
         if (A.field_mask & (1 << a)) {
             const double q0 = P.s0[a] + N.s0[a], q1 = P.s1[a] + N.s1[a], qe = P.se[a] + N.se[a];
             const double t0 = q0 + C.s0[a], t1 = q1 + C.s1[a], te = qe + C.se[a];
-            const double left = dpp_lower(t1, te);   // t at column y0-1
-            const double right = dpp_upper(t0, te);  // t at column y0+2
+            const double left = dpp_from_lower_lane(t1, te);   // t at column y0-1
+            const double right = dpp_from_upper_lane(t0, te);  // t at column y0+2
             w0 = C.d0[a] + ((left + t1) + q0);
             w1 = C.d1[a] + ((t0 + right) + q1);
         } else {
@@ -176,7 +141,7 @@ __device__ __forceinline__ void femit_row(const PassArgs& A, int r, int rmax, un
         v.y = w1;
         // lanes past W write the row's padding columns (never read as cells)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v),
-                                               frow_rsrc(A.out[a], r, rmax, A.pitch), voff, 0,
+                                               row_rsrc(A.out[a], r, rmax, A.pitch), voff, 0,
                                                (NT & 1) ? 2 : 0);
         if (REDUCE) {
             acc[a] = acc[a] + ((live && st1) ? w0 : 0.0);
@@ -195,13 +160,6 @@ __device__ __forceinline__ void fcopy_row(FRow<NA>& d, const FRow<NA>& s) {
         d.d0[a] = s.d0[a];
         d.d1[a] = s.d1[a];
     }
-}
-
-__device__ __forceinline__ double fwave_sum(double v) {
-    // fixed butterfly: every lane ends with the same, order-independent-of-timing value
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
 }
 
 // TH output rows per wave, fully unrolled; the wave mapping and row ranges are
@@ -236,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void mm_field_kernel(const PassArgs A) {
     // lane 0 carries the column left of the strip, lane 63 the one right of it
     const long long ye = lane == 0 ? base - 1 : (lane == 63 ? base + kStripCols : -1);
     const bool edge_ok = ye >= 0 && ye < W;
-    const int sy0 = span3f(W, y0), sy1 = span3f(W, y0 + 1), sye = edge_ok ? span3f(W, ye) : 0;
+    const int sy0 = span3(W, y0), sy1 = span3(W, y0 + 1), sye = edge_ok ? span3(W, ye) : 0;
     const bool fast_cols = base >= 2 && base + kStripCols <= W - 2;  // wave-uniform
     const bool st1 = y0 < W, st2 = y0 + 1 < W;
     const unsigned voff = (unsigned)(y0 * 8);
@@ -269,7 +227,7 @@ __global__ __launch_bounds__(kBlock) void mm_field_kernel(const PassArgs A) {
     if (REDUCE) {
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-            const double t = fwave_sum(acc[a]);
+            const double t = wave_sum(acc[a]);
             if (lane == 0) A.partials[(A.partial_base + wid) * NA + a] = t;
         }
     }
@@ -278,13 +236,9 @@ __global__ __launch_bounds__(kBlock) void mm_field_kernel(const PassArgs A) {
 template <int NA, int TH, int U, int NT>
 hipError_t launch_f(bool reduce, const PassArgs& a, hipStream_t s) {
     const long long blocks = (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (reduce)
-        hipLaunchKernelGGL((mm_field_kernel<NA, TH, U, true, NT>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((mm_field_kernel<NA, TH, U, false, NT>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_inst(reduce ? *inst_of<mm_field_kernel<NA, TH, U, true, NT>, kBlock>()
+                              : *inst_of<mm_field_kernel<NA, TH, U, false, NT>, kBlock>(),
+                       blocks, a, s);
 }
 
 // rows kept in flight per wave (each row: v and f of every attribute); fewer as the

@@ -21,6 +21,12 @@ constexpr int kSegPrefetch1 = 8;   // mm_passk.hpp seg_prefetch<1>() (MM_SEG_U1)
 constexpr int kWide20Waves = 4;    // waves per workgroup, K = 20 (mm_wide_k20.hip: 20 / MM_K20_KW)
 constexpr int kWideRingWaves = 4;  // the ring instance (mm_widear_k8.hip: 8 / MM_WIDEAR_KW)
 
+// 1 + (i > 0) + (i < n-1) inside [0, n), 0 outside: cnt = span(x)*span(y) - 1 (constexpr:
+// the kernels and the engine's host code share it)
+constexpr int span3(long long n, long long i) {
+    return (i >= 0 && i < n) ? 1 + (i > 0) + (i < n - 1) : 0;
+}
+
 inline int passk_out_cols(int k) { return kStripCols - 4 * ((k + 1) / 2); }
 
 inline int passk_max_steps(int na) { return na == 1 ? kMaxSteps : 2; }

@@ -1,5 +1,6 @@
-// mm_internal.hpp -- shared between the gfx950 kernels (mm_kernels.hip) and the
-// engine / C ABI (mm_engine.hip). Not part of the public boundary.
+// mm_internal.hpp -- shared between the gfx950 kernels (mm_kernels.hip, mm_field.hip,
+// mm_kernels_k.hip) and the engine / C ABI (mm_engine.hip). The K-step kernels' instances
+// and their launch: mm_inst.hpp. Not part of the public boundary.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,28 +48,6 @@ hipError_t launch_pass(int na, bool reduce, const PassArgs& a, hipStream_t s, in
 // ranges, wave mapping and partials as launch_pass; a.th 8, or 1 (border rows). variant bit
 // 0: non-temporal stores (one attribute).
 hipError_t launch_field(int na, bool reduce, const PassArgs& a, hipStream_t s, int variant);
-// K fused steps of a one-pass flow program (NA = 1: K 1..10, one diffusion; NA 2..4:
-// K 1..2, diffusions and transfer chains) on overlapped strips (mm_passk_kernel,
-// mm_kernels_k.hip). a.seg: segment schedule, a.th / a.th_edge rows per wave; else 4-row
-// blocks (a.th = 4). a.nstrips = ceil(W / passk_out_cols(k)). red: every level's sums into
-// partials[wave][k][na]. variant bit 0: non-temporal stores.
-hipError_t launch_passk(int k, int na, bool red, const PassArgs& a, hipStream_t s, int variant);
-// resident waves per CU of the segment kernel (occupancy API), 0 if unknown
-int passk_waves_per_cu(int k, int na, bool red, int nt);
-// Level-split K-step kernel (mm_wide_kernel) of a one-pass program with na attributes and
-// c columns per lane: na = 1 (one diffusion) with c = 4 for K in {4, 8, 12, 16, 20}; na = 4 (transfer chains + diffusions, config C5) with c = 2 for K in
-// {4, 8}. One workgroup of wide_waves_per_block(k, c, na) waves per strip segment, segment
-// schedule only (a.seg; a.th / a.th_edge rows per block, a.waves_a / a.waves_total count
-// BLOCKS), a.nstrips = ceil(W / wide_out_cols(k, c)). red: every level's sums into
-// partials[block][k][na]. variant (and nt) bit 0: non-temporal stores (the four-attribute
-// K = 8 instances store non-temporal whatever bit 0 says: only those are built); bit 1: four
-// attributes whose pre-chain is the ring t -> t+1 mod 4 and no post-chain (K = 8: the
-// compile-time-chain instance); bit 2: the pass has a post-chain (K = 8: the instance
-// that runs one); bits 4-6: K = 8, four attributes: the pass's attributes 0..N-1 diffuse,
-// the others do not (the engine relabels them so; the instance has N at compile time).
-int wide_blocks_per_cu(int k, int c, int na, bool red, int nt);
-hipError_t launch_wide(int k, int c, int na, bool red, const PassArgs& a, hipStream_t s,
-                       int variant);
 // Append the levels of `mask` (bit j: step j of a K-step pass) of partials[n][k][na],
 // each summed in a fixed order, to the history (na sums per entry).
 // perm: partials slot i holds attribute (perm >> 2i) & 3 (relabelled passes).

@@ -20,82 +20,17 @@
 // h..h+kGhost-1 are ghost rows (global row = x_init + local row).
 // Arithmetic order is the contract in oracle/mm_oracle.h; the .so is built with
 // -ffp-contract=off so no multiply/add pair is fused.
-#include "mm_internal.hpp"
+#include "mm_inst.hpp"
+#include "mm_lane.hpp"
 
 namespace mm {
 
 namespace {
 
-__device__ __forceinline__ double dpp_from_lower_lane(double src, double old) {
-    // lane i <- lane i-1 (wave_shr:1); lane 0 keeps `old`
-    const long long s = __double_as_longlong(src), o = __double_as_longlong(old);
-    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)s, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(s >> 32), 0x138, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double dpp_from_upper_lane(double src, double old) {
-    // lane i <- lane i+1 (wave_shl:1); lane 63 keeps `old`
-    const long long s = __double_as_longlong(src), o = __double_as_longlong(old);
-    const int lo = __builtin_amdgcn_update_dpp((int)o, (int)s, 0x130, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(o >> 32), (int)(s >> 32), 0x130, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// 1 + (i > 0) + (i < n-1) inside [0, n), 0 outside: cnt = span(x)*span(y) - 1
-__device__ __forceinline__ int span3(long long n, long long i) {
-    return (i >= 0 && i < n) ? 1 + (i > 0) + (i < n - 1) : 0;
-}
-
 // share of one emitter of the reference's single-source flow (src/Model.hpp:199); cnt ==
 // 8 as the exact *0.125
 __device__ __forceinline__ double share_of(double out, int cnt) {
     return cnt == 8 ? out * 0.125 : (cnt > 0 ? out / (double)cnt : 0.0);
-}
-
-// A neighbour's weight in the whole-grid step (oracle/mm_oracle.c c8_of): w = u * 8/cnt,
-// u itself for cnt == 8, 0 outside the grid -- each neighbour's share out/cnt is (r/8) * w.
-__device__ __forceinline__ double c8_one(int cnt) {
-    return cnt == 8 ? 1.0
-                    : (cnt == 5 ? 8.0 / 5.0
-                                : (cnt == 3 ? 8.0 / 3.0
-                                            : (cnt == 2 ? 4.0 : (cnt == 1 ? 8.0 : 0.0))));
-}
-
-// The own-weight coefficient of the box sum (oracle/mm_oracle.c m_of): -(8 + 8/cnt), 0 for a
-// cell without neighbours (it keeps its value) or outside the grid.
-__device__ __forceinline__ double m8_one(int cnt) {
-    return cnt == 8 ? -9.0
-                    : (cnt == 5 ? -(8.0 + 8.0 / 5.0)
-                                : (cnt == 3 ? -(8.0 + 8.0 / 3.0)
-                                            : (cnt == 2 ? -12.0 : (cnt == 1 ? -16.0 : 0.0))));
-}
-
-// Chain entries are read with compile-time indices only, so they are scalar loads of
-// the kernel arguments that the compiler hoists out of the row loop (a runtime index
-// into the by-value PassArgs turns into per-row global loads and vmcnt(0) waits that
-// drain the row prefetch). The attribute values sit in one 8-element register vector for
-// the chain, indexed by the wave-uniform a / b with s_set_gpr_idx (mm_passk.hpp chain_k);
-// a pad slot takes the outflows that leave the system.
-template <int NA>
-__device__ __forceinline__ void apply_chain(double (&u)[NA], int n, const signed char* ta,
-                                            const signed char* tb, const double* tr) {
-    static_assert(NA < 8, "one pad slot");
-    typedef double dv8 __attribute__((ext_vector_type(8)));
-    dv8 v;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < NA ? u[k] : 0.0;
-#pragma unroll
-    for (int t = 0; t < kMaxChain; ++t) {
-        if (t >= n) break;  // wave-uniform
-        const int a = ta[t];
-        const int b = tb[t] >= 0 ? tb[t] : 7;
-        const double out = tr[t] * v[a];
-        v[a] = v[a] - out;
-        v[b] = v[b] + out;
-    }
-#pragma unroll
-    for (int k = 0; k < NA; ++k) u[k] = v[k];
 }
 
 // Raw values of one row as this lane sees them: its two columns + its edge column.
@@ -112,24 +47,6 @@ struct ProcRow {
     double u0[NA], u1[NA];
     double m0, m1;
 };
-
-typedef double dv2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr unsigned kOOB = 0x80000000u;  // voffset past any num_records: loads 0, stores dropped
-
-// Buffer descriptor of local row r of one attribute buffer. Rows outside [0, rmax] get
-// num_records = 0: their loads return 0 and their stores are dropped with no memory
-// traffic, so every loop iteration issues the same memory instructions (the compiler
-// can then keep counted vmcnt waits across the loop instead of draining it).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const double* buf, int r, int rmax,
-                                                           long long pitch) {
-    const bool ok = r <= rmax;
-    const double* p = buf + (long long)(ok ? r : 0) * pitch;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), 0,
-                                             ok ? (int)(pitch * 8) : 0, 0x00020000);
-}
 
 // NT bit 1: non-temporal loads; bit 0: non-temporal stores
 template <int NA, int NT>
@@ -160,12 +77,12 @@ __device__ __forceinline__ void process_row(const PassArgs& A, int r, const RawR
         ue[a] = raw.ve[a];
     }
     if (CHAIN && A.npre) {
-        apply_chain<NA>(u0, A.npre, A.pre_a, A.pre_b, A.pre_r);
-        apply_chain<NA>(u1, A.npre, A.pre_a, A.pre_b, A.pre_r);
-        apply_chain<NA>(ue, A.npre, A.pre_a, A.pre_b, A.pre_r);
+        chain_k<NA>(u0, A.npre, A.pre_a, A.pre_b, A.pre_r);
+        chain_k<NA>(u1, A.npre, A.pre_a, A.pre_b, A.pre_r);
+        chain_k<NA>(ue, A.npre, A.pre_a, A.pre_b, A.pre_r);
     }
-    o.m0 = m8_one(sx * sy0 - 1);
-    o.m1 = m8_one(sx * sy1 - 1);
+    o.m0 = m8_of(sx * sy0 - 1);
+    o.m1 = m8_of(sx * sy1 - 1);
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         o.u0[a] = u0[a];
@@ -183,7 +100,7 @@ __device__ __forceinline__ void process_row(const PassArgs& A, int r, const RawR
     }
     // (sx == 0: a row outside the global grid weighs 0; a column outside it -- the pitch
     // padding -- weighs 0 by select, so no value it holds reaches a cell)
-    const double c0 = c8_one(sx * sy0 - 1), c1 = c8_one(sx * sy1 - 1), ce = c8_one(sx * sye - 1);
+    const double c0 = c8_of(sx * sy0 - 1), c1 = c8_of(sx * sy1 - 1), ce = c8_of(sx * sye - 1);
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         const bool dif = A.diffuse_mask & (1 << a);
@@ -228,8 +145,8 @@ __device__ __forceinline__ void emit_row(const PassArgs& A, int r, int rmax, uns
         }
     }
     if (CHAIN && A.npost) {
-        apply_chain<NA>(w0, A.npost, A.post_a, A.post_b, A.post_r);
-        apply_chain<NA>(w1, A.npost, A.post_a, A.post_b, A.post_r);
+        chain_k<NA>(w0, A.npost, A.post_a, A.post_b, A.post_r);
+        chain_k<NA>(w1, A.npost, A.post_a, A.post_b, A.post_r);
     }
     const bool live = r <= rmax;  // wave-uniform
 #pragma unroll
@@ -260,13 +177,6 @@ __device__ __forceinline__ void copy_row(ProcRow<NA>& d, const ProcRow<NA>& s) {
     }
     d.m0 = s.m0;
     d.m1 = s.m1;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    // fixed butterfly: every lane ends with the same, order-independent-of-timing value
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
 }
 
 // TH output rows per wave, fully unrolled (no loop back edge, so the compiler keeps
@@ -453,13 +363,9 @@ __global__ void mm_sum_partials_kernel(const double* partials, long long n, doub
 template <int NA, int TH, int U, int NT, bool CHAIN>
 hipError_t launch_c(bool reduce, const PassArgs& a, hipStream_t s) {
     const long long blocks = (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (reduce)
-        hipLaunchKernelGGL((mm_pass_kernel<NA, TH, U, true, NT, CHAIN>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, a);
-    else
-        hipLaunchKernelGGL((mm_pass_kernel<NA, TH, U, false, NT, CHAIN>), dim3((unsigned)blocks),
-                           dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+    return launch_inst(reduce ? *inst_of<mm_pass_kernel<NA, TH, U, true, NT, CHAIN>, kBlock>()
+                              : *inst_of<mm_pass_kernel<NA, TH, U, false, NT, CHAIN>, kBlock>(),
+                       blocks, a, s);
 }
 
 // One attribute, no transfers: the headline Exponencial step. Row block TH in

@@ -1,6 +1,6 @@
-// mm_kernels_k.hip -- dispatch of the K-step kernels (templates: mm_passk.hpp and
-// mm_wide.hpp, instances: mm_passk_k1..10.hip, mm_wide_k*.hip) and the fixed-order
-// level-sum finalize kernel.
+// mm_kernels_k.hip -- the K-step kernels' one table of instances (templates: mm_passk.hpp
+// and mm_wide.hpp; instance units with their lookups: mm_passk_k1..10.hip, mm_wide*.hip),
+// their launch, and the fixed-order level-sum finalize kernel.
 #include "mm_wide.hpp"
 
 namespace mm {
@@ -64,107 +64,39 @@ hipError_t launch_finalize_levels(const double* partials, long long n, int k, in
     return hipGetLastError();
 }
 
-static_assert(seg_prefetch<1>() == kSegPrefetch1, "mm_geom.hpp: passk_max_rows counts MM_SEG_U1 rows");
+static_assert(seg_prefetch<1>() == kSegPrefetch1,
+              "mm_geom.hpp: passk_max_rows counts MM_SEG_U1 rows");
 
-int passk_waves_per_cu(int k, int na, bool red, int nt) {
-    switch (k) {
-        case 1: return passk_waves_k1(na, red, nt);
-        case 2: return passk_waves_k2(na, red, nt);
-        case 3: return passk_waves_k3(na, red, nt);
-        case 4: return passk_waves_k4(na, red, nt);
-        case 5: return passk_waves_k5(na, red, nt);
-        case 6: return passk_waves_k6(na, red, nt);
-        case 7: return passk_waves_k7(na, red, nt);
-        case 8: return passk_waves_k8(na, red, nt);
-        case 9: return passk_waves_k9(na, red, nt);
-        case 10: return passk_waves_k10(na, red, nt);
-        default: return 0;
-    }
+// Every instance unit's lookup; each answers for its own keys alone.
+const KernelInst* find_inst(const InstKey& q) {
+    static constexpr InstLookup kUnits[] = {
+        passk_inst_k1,     passk_inst_k2,     passk_inst_k3,     passk_inst_k4,
+        passk_inst_k5,     passk_inst_k6,     passk_inst_k7,     passk_inst_k8,
+        passk_inst_k9,     passk_inst_k10,    wide_inst_k4,      wide_inst_k8,
+        wide_inst_k12,     wide_inst_k16,     wide_inst_k20,     widea_inst_k4,
+        widear_inst_k8,    widea8_inst_n1_p0, widea8_inst_n1_p1, widea8_inst_n2_p0,
+        widea8_inst_n2_p1, widea8_inst_n3_p0, widea8_inst_n3_p1, widea8_inst_n4_p0,
+        widea8_inst_n4_p1};
+    for (InstLookup unit : kUnits)
+        if (const KernelInst* inst = unit(q)) return inst;
+    return nullptr;
 }
 
 // A pass of no work is not launched -- unless waves_a < 0 marks it as mm_prepare's
 // priming dispatch: one workgroup that leaves at its first instruction (waves_total = 0),
 // which loads the kernel and sizes the queue's scratch for it ahead of the run.
-hipError_t launch_passk(int k, int na, bool red, const PassArgs& a, hipStream_t s, int variant) {
+hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s) {
     if (a.waves_total <= 0 && a.waves_a >= 0) return hipSuccess;
-    switch (k) {
-        case 1: return passk_launch_k1(na, red, a, s, variant);
-        case 2: return passk_launch_k2(na, red, a, s, variant);
-        case 3: return passk_launch_k3(na, red, a, s, variant);
-        case 4: return passk_launch_k4(na, red, a, s, variant);
-        case 5: return passk_launch_k5(na, red, a, s, variant);
-        case 6: return passk_launch_k6(na, red, a, s, variant);
-        case 7: return passk_launch_k7(na, red, a, s, variant);
-        case 8: return passk_launch_k8(na, red, a, s, variant);
-        case 9: return passk_launch_k9(na, red, a, s, variant);
-        case 10: return passk_launch_k10(na, red, a, s, variant);
-        default: return hipErrorInvalidValue;
+    const KernelInst* inst = find_inst(q);
+    if (!inst) return hipErrorInvalidValue;
+    // at least one workgroup: a dispatch with no work (mm_prepare) still reaches the queue
+    long long blocks = std::max<long long>(a.waves_total, 1);  // mm_wide_kernel: one per segment
+    if (q.family == kInstPassK) {
+        if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
+        blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
+        if (a.xcd_remap) blocks = (blocks + 7) / 8 * 8;
     }
-}
-
-namespace {
-
-// The K = 8 four-attribute instance of a variant: (nd - 1) * 2 + post, -1 if none.
-int widea8_index(int variant) {
-    const int nd = (variant >> 4) & 7, post = (variant >> 2) & 1;
-    return nd >= 1 && nd <= 4 ? (nd - 1) * 2 + post : -1;
-}
-
-}  // namespace
-
-int wide_blocks_per_cu(int k, int c, int na, bool red, int nt) {
-    if (!wide_has(k, c, na)) return 0;
-    if (na > 1 && k == 8 && (nt & 2)) return widear_blocks_k8(na, red, nt & 1);
-    if (na > 1 && k == 4) return widea_blocks_k4(na, red, nt & 1);
-    if (na > 1) {
-        switch (widea8_index(nt)) {
-            case 0: return widea8_blocks_n1_p0(red);
-            case 1: return widea8_blocks_n1_p1(red);
-            case 2: return widea8_blocks_n2_p0(red);
-            case 3: return widea8_blocks_n2_p1(red);
-            case 4: return widea8_blocks_n3_p0(red);
-            case 5: return widea8_blocks_n3_p1(red);
-            case 6: return widea8_blocks_n4_p0(red);
-            case 7: return widea8_blocks_n4_p1(red);
-            default: return 0;
-        }
-    }
-    nt &= 1;
-    switch (k) {
-        case 4: return wide_blocks_k4(red, nt);
-        case 8: return wide_blocks_k8(red, nt);
-        case 12: return wide_blocks_k12(red, nt);
-        case 16: return wide_blocks_k16(red, nt);
-        default: return wide_blocks_k20(red, nt);
-    }
-}
-
-hipError_t launch_wide(int k, int c, int na, bool red, const PassArgs& a, hipStream_t s,
-                       int variant) {
-    if (a.waves_total <= 0 && a.waves_a >= 0) return hipSuccess;  // (waves_a < 0: priming)
-    if (!wide_has(k, c, na)) return hipErrorInvalidValue;
-    if (na > 1 && k == 8 && (variant & 2)) return widear_launch_k8(na, red, a, s, variant & 1);
-    if (na > 1 && k == 4) return widea_launch_k4(na, red, a, s, variant & 1);
-    if (na > 1) {
-        switch (widea8_index(variant)) {
-            case 0: return widea8_launch_n1_p0(red, a, s);
-            case 1: return widea8_launch_n1_p1(red, a, s);
-            case 2: return widea8_launch_n2_p0(red, a, s);
-            case 3: return widea8_launch_n2_p1(red, a, s);
-            case 4: return widea8_launch_n3_p0(red, a, s);
-            case 5: return widea8_launch_n3_p1(red, a, s);
-            case 6: return widea8_launch_n4_p0(red, a, s);
-            case 7: return widea8_launch_n4_p1(red, a, s);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (k) {
-        case 4: return wide_launch_k4(red, a, s, variant);
-        case 8: return wide_launch_k8(red, a, s, variant);
-        case 12: return wide_launch_k12(red, a, s, variant);
-        case 16: return wide_launch_k16(red, a, s, variant);
-        default: return wide_launch_k20(red, a, s, variant);
-    }
+    return launch_inst(*inst, blocks, a, s);
 }
 
 }  // namespace mm

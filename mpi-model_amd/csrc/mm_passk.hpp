@@ -45,37 +45,14 @@
 // translation unit per K so the builds run in parallel) and mm_kernels_k.hip dispatches.
 #pragma once
 
-#include <algorithm>
-
-#include "mm_internal.hpp"
+#include "mm_inst.hpp"
+#include "mm_lane.hpp"
 
 namespace mm {
 
-// per-K entry points (mm_passk_k1.hip .. mm_passk_k8.hip); na outside the TU's set is
-// hipErrorInvalidValue / 0
-#define MM_PASSK_DECL(K)                                                                  \
-    hipError_t passk_launch_k##K(int na, bool red, const PassArgs& a, hipStream_t s, int v); \
-    int passk_waves_k##K(int na, bool red, int nt);
-MM_PASSK_DECL(1)
-MM_PASSK_DECL(2)
-MM_PASSK_DECL(3)
-MM_PASSK_DECL(4)
-MM_PASSK_DECL(5)
-MM_PASSK_DECL(6)
-MM_PASSK_DECL(7)
-MM_PASSK_DECL(8)
-MM_PASSK_DECL(9)
-MM_PASSK_DECL(10)
-#undef MM_PASSK_DECL
-
 namespace {
 
-
-typedef double dv2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOBk = 0x80000000u;  // voffset past any num_records: load 0 / drop store
-constexpr int kSeg = 0;                  // MODE value of the segment schedule
+constexpr int kSeg = 0;  // MODE value of the segment schedule
 
 #ifndef MM_PASSK_MIN_WAVES
 #define MM_PASSK_MIN_WAVES 1  // __launch_bounds__ minimum waves per SIMD (caps VGPRs)
@@ -99,40 +76,10 @@ constexpr int seg_prefetch() {
     return NA == 1 ? MM_SEG_U1 : (NA == 2 ? 4 : MM_SEG_UN);
 }
 
-// mov_dpp has no tied "old" operand, so the result can land in a fresh register without
-// first copying the source; lanes without a source lane read 0 (bound_ctrl) -- only the
-// halo lanes at the wave's edges, whose results are discarded.
-__device__ __forceinline__ double dpp_lower(double src) {
-    // lane i <- lane i-1 (wave_shr:1)
-    const long long s = __double_as_longlong(src);
-    const int lo = __builtin_amdgcn_mov_dpp((int)s, 0x138, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(s >> 32), 0x138, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double dpp_upper(double src) {
-    // lane i <- lane i+1 (wave_shl:1)
-    const long long s = __double_as_longlong(src);
-    const int lo = __builtin_amdgcn_mov_dpp((int)s, 0x130, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp((int)(s >> 32), 0x130, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// The same two shifts through the LDS crossbar (ds_bpermute_b32: no LDS memory, the DS
-// pipe instead of the VALU). A DPP shift of a double is two VALU moves, 4 of the 18 VALU
-// instructions of a level-row of two columns; ds_bpermute moves them to the otherwise idle
-// DS pipe. `addr` = 4 * source lane (wraps around the wave: the halo lanes get garbage
-// instead of 0, and their results are discarded either way).
+// 1: the two lane shifts through the LDS crossbar (mm_lane.hpp lds_shift), not DPP
 #ifndef MM_SHIFT_LDS
 #define MM_SHIFT_LDS 0
 #endif
-__device__ __forceinline__ double lds_shift(double src, int addr) {
-    const long long s = __double_as_longlong(src);
-    const int lo = __builtin_amdgcn_ds_bpermute(addr, (int)s);
-    const int hi = __builtin_amdgcn_ds_bpermute(addr, (int)(s >> 32));
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 // A prefetched row is copied out of its ring slot where it is consumed (U rows after its
 // load was issued). Without the copy the slot's registers become the level's d = u - out
 // (v_fmac works in place), every reload lands in fresh registers, and the loop's back edge
@@ -147,34 +94,9 @@ __device__ __forceinline__ double vcopy(double x) {
     return y;
 }
 
-// 1 + (i > 0) + (i < n-1) inside [0, n), 0 outside: cnt = span(x)*span(y) - 1
-__device__ __forceinline__ int span3k(long long n, long long i) {
-    return (i >= 0 && i < n) ? 1 + (i > 0) + (i < n - 1) : 0;
-}
-
-// A neighbour's weight factor 8/cnt (oracle/mm_oracle.c c8_of: w = u * 8/cnt, 1 for an
-// interior cell, 0 outside the grid): the correctly rounded quotients as constants.
-__device__ __forceinline__ double c8k(int cnt) {
-    return cnt == 8 ? 1.0
-                    : (cnt == 5 ? 8.0 / 5.0
-                                : (cnt == 3 ? 8.0 / 3.0
-                                            : (cnt == 2 ? 4.0 : (cnt == 1 ? 8.0 : 0.0))));
-}
-
-// The own-weight coefficient -(8 + 8/cnt) of the box sum (oracle/mm_oracle.c m_of): -9 for
-// an interior cell, 0 for a cell without neighbours (it keeps its value) or outside the grid.
-constexpr double kM8 = -9.0;
-constexpr double kM5 = -(8.0 + 8.0 / 5.0);
-__device__ __forceinline__ double m8k(int cnt) {
-    return cnt == 8 ? kM8
-                    : (cnt == 5 ? kM5
-                                : (cnt == 3 ? -(8.0 + 8.0 / 3.0)
-                                            : (cnt == 2 ? -12.0 : (cnt == 1 ? -16.0 : 0.0))));
-}
-
 // Descriptor of `rows` consecutive rows starting at `first` (pointer already offset):
 // row k of the range is at byte offset k*pitch*8 (added to the lane's voffset), offsets
-// past the range -- later rows, or lanes whose voffset is kOOBk -- load 0 / drop stores.
+// past the range -- later rows, or lanes whose voffset is kOOB -- load 0 / drop stores.
 // One descriptor per wave and attribute instead of one per row keeps the unrolled rows
 // from holding dozens of scalar descriptors (which spilled SGPRs into VGPR lanes). The
 // engine keeps every offset below 2^31 (passk_max_rows).
@@ -217,36 +139,6 @@ struct Lane {
     int from_lower, from_upper;  // ds_bpermute byte addresses of lanes i-1, i+1 (MM_SHIFT_LDS)
 };
 
-// Transfers of a chain, in declared order, on one cell's attribute values: out = r*u_a;
-// u_a -= out; u_b += out (b < 0: the outflow leaves the system). a and b are wave-uniform
-// kernel arguments. The values sit in one 8-element register vector for the chain -- at
-// that width LLVM indexes it with s_set_gpr_idx (two v_mov per access) instead of a
-// select over every attribute per operand (36 v_cndmask per transfer and column) -- and a
-// pad slot takes the outflows that leave the system.
-typedef double dv8 __attribute__((ext_vector_type(8)));
-#ifndef MM_CHAIN_CAP
-#define MM_CHAIN_CAP kMaxChain  // transfers a chain may hold (tuning: fewer unrolled slots)
-#endif
-template <int NA>
-__device__ __forceinline__ void chain_k(double (&u)[NA], int n, const signed char* ta,
-                                        const signed char* tb, const double* tr) {
-    static_assert(NA < 8, "one pad slot");
-    dv8 v;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = k < NA ? u[k] : 0.0;
-#pragma unroll
-    for (int t = 0; t < MM_CHAIN_CAP; ++t) {
-        if (t >= n) break;  // wave-uniform
-        const int a = ta[t];
-        const int b = tb[t] >= 0 ? tb[t] : 7;
-        const double out = tr[t] * v[a];
-        v[a] = v[a] - out;
-        v[b] = v[b] + out;
-    }
-#pragma unroll
-    for (int k = 0; k < NA; ++k) u[k] = v[k];
-}
-
 // Pre-chain, then per diffusing attribute the weights w = u * 8/cnt of this lane's two
 // columns of row gx (oracle/mm_oracle.c w_row: each neighbour's share out/cnt = (r/8) * w,
 // src/Exponencial.hpp:18-20, src/Model.hpp:199); cells outside the grid weigh 0;
@@ -259,7 +151,7 @@ __device__ __forceinline__ void proc_n(const PassArgs& A, const Lane& c, long lo
         chain_k<NA>(u0, A.npre, A.pre_a, A.pre_b, A.pre_r);
         chain_k<NA>(u1, A.npre, A.pre_a, A.pre_b, A.pre_r);
     }
-    const int sx = FAST ? 3 : span3k(c.H, gx);
+    const int sx = FAST ? 3 : span3(c.H, gx);
     const bool inner = FAST || (sx == 3 && c.fast_cols);  // wave-uniform
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
@@ -270,8 +162,8 @@ __device__ __forceinline__ void proc_n(const PassArgs& A, const Lane& c, long lo
             w1[a] = u1[a];
         } else {  // a column outside the grid (span 0: its pitch padding) weighs 0 by select,
                   // so no value it holds reaches a cell
-            w0[a] = c.sy0 == 0 ? 0.0 : u0[a] * c8k(sx * c.sy0 - 1);
-            w1[a] = c.sy1 == 0 ? 0.0 : u1[a] * c8k(sx * c.sy1 - 1);
+            w0[a] = c.sy0 == 0 ? 0.0 : u0[a] * c8_of(sx * c.sy0 - 1);
+            w1[a] = c.sy1 == 0 ? 0.0 : u1[a] * c8_of(sx * c.sy1 - 1);
         }
     }
 }
@@ -316,9 +208,9 @@ __device__ __forceinline__ void level_emit(const PassArgs& A, const Lane& c, lon
                                            double (&o0)[NA], double (&o1)[NA]) {
     double wn0[NA], wn1[NA];
     proc_n<NA, FAST, CHAIN>(A, c, gx, u0, u1, wn0, wn1);
-    const int sxm = FAST ? 3 : span3k(c.H, gx - 1);  // the emitted row
-    const double m0 = FAST ? kM8 : m8k(sxm * c.sy0 - 1);
-    const double m1 = FAST ? kM8 : m8k(sxm * c.sy1 - 1);
+    const int sxm = FAST ? 3 : span3(c.H, gx - 1);  // the emitted row
+    const double m0 = FAST ? kM8 : m8_of(sxm * c.sy0 - 1);
+    const double m1 = FAST ? kM8 : m8_of(sxm * c.sy1 - 1);
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         double na0, na1;  // the window's next wa
@@ -374,12 +266,6 @@ __device__ __forceinline__ void accum(double& acc, bool own, const Lane& c, doub
     asm volatile("" : "+v"(acc));
 }
 
-__device__ __forceinline__ double wave_sum_k(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
-}
-
 template <int K, int NA>
 __device__ __forceinline__ void write_sums(const PassArgs& A, long long wid, int lane,
                                            double (&acc)[K][NA]) {
@@ -387,7 +273,7 @@ __device__ __forceinline__ void write_sums(const PassArgs& A, long long wid, int
     for (int j = 0; j < K; ++j)
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-            const double t = wave_sum_k(acc[j][a]);
+            const double t = wave_sum(acc[j][a]);
             if (lane == 0) A.partials[((A.partial_base + wid) * K + j) * NA + a] = t;
         }
 }
@@ -718,15 +604,15 @@ __global__ __launch_bounds__(kBlock, MM_PASSK_MIN_WAVES) void mm_passk_kernel(co
     const long long c0 = (long long)strip * OC - 2 * L;  // first loaded column (even)
     const long long y0 = c0 + 2 * lane;
     const bool in_row = y0 >= 0 && y0 < A.pitch;  // y0 even, pitch a multiple of 128
-    const unsigned voff = in_row ? (unsigned)(y0 * 8) : kOOBk;
+    const unsigned voff = in_row ? (unsigned)(y0 * 8) : kOOB;
     const bool store_lane = lane >= L && lane < 64 - L && y0 < W;
     // columns past W inside the pitch are padding: writing them is harmless
-    const unsigned soff = store_lane ? (unsigned)(y0 * 8) : kOOBk;
+    const unsigned soff = store_lane ? (unsigned)(y0 * 8) : kOOB;
     Lane c;
     c.H = A.H;
     c.gx0 = A.x_init;
-    c.sy0 = span3k(W, y0);
-    c.sy1 = span3k(W, y0 + 1);
+    c.sy0 = span3(W, y0);
+    c.sy1 = span3(W, y0 + 1);
     c.fast_cols = c0 >= 1 && c0 + kStripCols <= W - 1;  // loaded cols in [1, W-2]
     c.own0 = store_lane;
     c.own1 = store_lane && y0 + 1 < W;
@@ -763,58 +649,21 @@ __global__ __launch_bounds__(kBlock, MM_PASSK_MIN_WAVES) void mm_passk_kernel(co
     }
 }
 
-template <int K, int MODE, int U, int NT, int NA, bool CHAIN>
-hipError_t launch_k3(bool red, const PassArgs& a, hipStream_t s) {
-    // at least one block: a dispatch with no work (mm_prepare) still reaches the queue
-    long long blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (a.xcd_remap) blocks = (blocks + 7) / 8 * 8;
-    const dim3 g((unsigned)blocks), b(kBlock);
-    (void)hipGetLastError();  // the status below is this launch's, not an earlier call's
-    if (red)
-        hipLaunchKernelGGL((mm_passk_kernel<K, MODE, U, true, NT, NA, CHAIN>), g, b, 0, s, a);
-    else
-        hipLaunchKernelGGL((mm_passk_kernel<K, MODE, U, false, NT, NA, CHAIN>), g, b, 0, s, a);
-    return hipGetLastError();
-}
-
-// a.seg: segment schedule (variant bit 0: non-temporal stores); else 4-row blocks.
+// The instances of one (K, NA): the segment schedule with or without non-temporal stores,
+// the border blocks of kBorderRows rows (at most 4 rows prefetched; q.nt does not apply),
+// each with the step sums or without. nullptr for another kernel's key.
 template <int K, int NA, bool CHAIN>
-hipError_t launch_k2(bool red, const PassArgs& a, hipStream_t s, int v) {
-    constexpr int U = seg_prefetch<NA>();
-    if (!a.seg) {
-        if (a.th != kBorderRows) return hipErrorInvalidValue;
-        return launch_k3<K, kBorderRows, (U < 4 ? U : 4), 0, NA, CHAIN>(red, a, s);
-    }
-    return (v & 1) ? launch_k3<K, kSeg, U, 1, NA, CHAIN>(red, a, s)
-                   : launch_k3<K, kSeg, U, 0, NA, CHAIN>(red, a, s);
-}
-
-// Resident blocks per CU of the segment kernel, from its register count: gfx950 gives each
-// SIMD lane 512 registers (VGPRs and AGPRs together, allocated in granules of 8), at most
-// 8 waves per SIMD, 4 SIMDs per CU (MI355X_MICROARCH.md). The runtime's occupancy query is
-// not used: after `import torch` it answers for this kernel with half the true occupancy
-// (profiles/r02/occupancy_probe.log), which would halve the waves of every plan.
-template <int K, int NA, bool CHAIN, bool RED, int NT>
-int seg_blocks_per_cu_v() {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(
-        &fa, reinterpret_cast<const void*>(mm_passk_kernel<K, kSeg, seg_prefetch<NA>(), RED, NT, NA, CHAIN>));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // a failed query must not surface at the next launch
-        return 0;
-    }
-    const int regs = (fa.numRegs + 7) / 8 * 8;
-    const int waves_per_simd = regs > 0 ? std::min(8, 512 / regs) : 8;
-    return waves_per_simd * 4 / kWavesPerBlock;
-}
-
-template <int K, int NA, bool CHAIN>
-int seg_blocks_per_cu(bool red, int nt) {
-    if (red)
-        return nt ? seg_blocks_per_cu_v<K, NA, CHAIN, true, 1>()
-                  : seg_blocks_per_cu_v<K, NA, CHAIN, true, 0>();
-    return nt ? seg_blocks_per_cu_v<K, NA, CHAIN, false, 1>()
-              : seg_blocks_per_cu_v<K, NA, CHAIN, false, 0>();
+const KernelInst* passk_inst(const InstKey& q) {
+    constexpr int U = seg_prefetch<NA>(), UB = U < 4 ? U : 4;
+    if (q.family != kInstPassK || q.k != K || q.na != NA || q.cols != 2) return nullptr;
+    if (!q.seg)
+        return q.red ? inst_of<mm_passk_kernel<K, kBorderRows, UB, true, 0, NA, CHAIN>, kBlock>()
+                     : inst_of<mm_passk_kernel<K, kBorderRows, UB, false, 0, NA, CHAIN>, kBlock>();
+    if (q.nt)
+        return q.red ? inst_of<mm_passk_kernel<K, kSeg, U, true, 1, NA, CHAIN>, kBlock>()
+                     : inst_of<mm_passk_kernel<K, kSeg, U, false, 1, NA, CHAIN>, kBlock>();
+    return q.red ? inst_of<mm_passk_kernel<K, kSeg, U, true, 0, NA, CHAIN>, kBlock>()
+                 : inst_of<mm_passk_kernel<K, kSeg, U, false, 0, NA, CHAIN>, kBlock>();
 }
 
 }  // namespace

@@ -3,17 +3,10 @@
 
 namespace mm {
 
-hipError_t passk_launch_k4(int na, bool red, const PassArgs& a, hipStream_t s, int v) {
-    switch (na) {
-        case 1: return launch_k2<4, 1, false>(red, a, s, v);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-int passk_waves_k4(int na, bool red, int nt) {
-    switch (na) {
-        case 1: return seg_blocks_per_cu<4, 1, false>(red, nt) * kWavesPerBlock;
-        default: return 0;
+const KernelInst* passk_inst_k4(const InstKey& q) {
+    switch (q.na) {
+        case 1: return passk_inst<4, 1, false>(q);
+        default: return nullptr;
     }
 }
 

@@ -57,38 +57,6 @@
 
 namespace mm {
 
-// per-K entry points (mm_wide_k*.hip: one attribute, C = 4)
-#define MM_WIDE_DECL(K)                                                                    \
-    hipError_t wide_launch_k##K(bool red, const PassArgs& a, hipStream_t s, int v);       \
-    int wide_blocks_k##K(bool red, int nt);
-MM_WIDE_DECL(4)
-MM_WIDE_DECL(8)
-MM_WIDE_DECL(12)
-MM_WIDE_DECL(16)
-MM_WIDE_DECL(20)
-#undef MM_WIDE_DECL
-// four attributes, 2 columns per lane. K = 4 (mm_widea_k4.hip): any pass.
-hipError_t widea_launch_k4(int na, bool red, const PassArgs& a, hipStream_t s, int v);
-int widea_blocks_k4(int na, bool red, int nt);
-// K = 8 (mm_widea_k8.hip, one object per instance): the first N attributes diffuse (the
-// engine relabels the attributes so that the diffusing ones come first), with (P = 1) or
-// without (P = 0) a post-chain; non-temporal stores.
-#define MM_WIDEA8_DECL(N, P)                                                               \
-    hipError_t widea8_launch_n##N##_p##P(bool red, const PassArgs& a, hipStream_t s);     \
-    int widea8_blocks_n##N##_p##P(bool red);
-MM_WIDEA8_DECL(1, 0)
-MM_WIDEA8_DECL(2, 0)
-MM_WIDEA8_DECL(3, 0)
-MM_WIDEA8_DECL(4, 0)
-MM_WIDEA8_DECL(1, 1)
-MM_WIDEA8_DECL(2, 1)
-MM_WIDEA8_DECL(3, 1)
-MM_WIDEA8_DECL(4, 1)
-#undef MM_WIDEA8_DECL
-// four attributes whose pre-chain is the ring t -> t+1 mod 4 (mm_widear_k*.hip)
-hipError_t widear_launch_k8(int na, bool red, const PassArgs& a, hipStream_t s, int v);
-int widear_blocks_k8(int na, bool red, int nt);
-
 namespace {
 
 #ifndef MM_WIDE_U
@@ -137,15 +105,6 @@ struct WinC {
     double wa[C], wm[C], um[C];
 };
 
-// 8/cnt for the neighbour counts a cell can have (oracle/mm_oracle.c c8_of): the same
-// correctly rounded quotients, no division at run time
-__device__ __forceinline__ double c8_of(int cnt) {
-    return cnt == 8 ? 1.0
-                    : (cnt == 5 ? 8.0 / 5.0
-                                : (cnt == 3 ? 8.0 / 3.0
-                                            : (cnt == 2 ? 4.0 : (cnt == 1 ? 8.0 : 0.0))));
-}
-
 // The weights w of this lane's columns of row gx (oracle/mm_oracle.c w_row). FAST:
 // interior row of an interior strip, w = u. EDGE: interior row of a strip holding the
 // grid's first (or last) column as a lane's column 0 (C-1), the columns past it in whole
@@ -166,7 +125,7 @@ __device__ __forceinline__ void procc(const WLane<C>& c, long long gx, const dou
         w[0] = c.eL ? w0 : w[0];
         w[C - 1] = c.eR ? w1 : w[C - 1];
     } else if (BODY == kBodyGen) {
-        const int sx = span3k(c.H, gx);
+        const int sx = span3(c.H, gx);
         if (!MM_WIDE_GEN_ROW || c.gen) {
 #pragma unroll
             for (int k = 0; k < C; ++k) w[k] = u[k] * c8_of(sx * c.sy[k] - 1);
@@ -242,12 +201,12 @@ __device__ __forceinline__ void wemit(const WLane<C>& c, double r8, long long gx
         m[0] = c.eL ? kM5 : m[0];
         m[C - 1] = c.eR ? kM5 : m[C - 1];
     } else if (BODY == kBodyGen) {
-        const int sxm = span3k(c.H, gx - 1);
+        const int sxm = span3(c.H, gx - 1);
         if (!MM_WIDE_GEN_ROW || c.gen) {
 #pragma unroll
-            for (int k = 0; k < C; ++k) m[k] = m8k(sxm * c.sy[k] - 1);
+            for (int k = 0; k < C; ++k) m[k] = m8_of(sxm * c.sy[k] - 1);
         } else {
-            const double mr = m8k(3 * sxm - 1), me = m8k(2 * sxm - 1);
+            const double mr = m8_of(3 * sxm - 1), me = m8_of(2 * sxm - 1);
 #pragma unroll
             for (int k = 0; k < C; ++k) m[k] = mr;
             m[0] = c.eL ? me : mr;
@@ -823,7 +782,7 @@ __device__ __forceinline__ void wave_run(const WCtx<C, NA>& x, int iend,
         for (int q = 0; q < KW; ++q) {
 #pragma unroll
             for (int a = 0; a < NA; ++a)
-                carry[q][a] = carry[q][a] + wave_sum_k(lane_owns ? st.acc[q][a] : 0.0);
+                carry[q][a] = carry[q][a] + wave_sum(lane_owns ? st.acc[q][a] : 0.0);
         }
     }
 }
@@ -877,13 +836,13 @@ __device__ __forceinline__ void wide_segment(const PassArgs& A, dv2* lds, int p,
     x.rowb = (unsigned)(A.pitch * 8);
     // input row k of the segment is row k - sh of the descriptor (base row rA - K): row -1
     // wraps past num_records (loads 0) in every lane that loads inside the pitch
-    x.voff = (in_row ? (unsigned)(y0 * 8) : kOOBk) - (unsigned)sh * x.rowb;
+    x.voff = (in_row ? (unsigned)(y0 * 8) : kOOB) - (unsigned)sh * x.rowb;
     // columns past W inside the pitch are padding: writing them is harmless
-    x.soff = store_lane ? (unsigned)(y0 * 8) : kOOBk;
+    x.soff = store_lane ? (unsigned)(y0 * 8) : kOOB;
     x.c.H = A.H;
 #pragma unroll
     for (int k = 0; k < C; ++k) {
-        x.c.sy[k] = span3k(W, y0 + k);
+        x.c.sy[k] = span3(W, y0 + k);
         x.c.own[k] = store_lane && y0 + k < W;
         x.c.ownw[k] = x.c.own[k] ? 1.0 : 0.0;
     }
@@ -979,65 +938,27 @@ __global__ __launch_bounds__(64 * P, MW) void mm_wide_kernel(const PassArgs A) {
     }
 }
 
-template <int C, int NA, int KW, int P, int MW, int NT>
-hipError_t wide_launch3(bool red, const PassArgs& a, hipStream_t s) {
-    constexpr int U = MM_WIDE_U;
-    // at least one workgroup: a dispatch with no work (mm_prepare) still reaches the queue
-    const dim3 g((unsigned)std::max<long long>(a.waves_total, 1)), b(64 * P);
-    (void)hipGetLastError();  // the status below is this launch's, not an earlier call's
-    if (red)
-        hipLaunchKernelGGL((mm_wide_kernel<C, NA, KW, P, MW, U, MM_WIDE_B, true, NT>), g, b, 0, s, a);
-    else
-        hipLaunchKernelGGL((mm_wide_kernel<C, NA, KW, P, MW, U, MM_WIDE_B, false, NT>), g, b, 0, s, a);
-    return hipGetLastError();
+// Does the key select this shape of mm_wide_kernel? (Segment schedule only.)
+template <int C, int NA, int KW, int P>
+bool wide_key(const InstKey& q) {
+    return q.family == kInstWide && q.k == KW * P && q.cols == C && q.na == NA && q.seg;
 }
 
 // one instance (a translation unit per instance builds in parallel: mm_wide_k20.hip)
 template <int C, int NA, int KW, int P, int MW, bool RED, int NT>
-hipError_t wide_launch4(const PassArgs& a, hipStream_t s) {
-    if (!a.seg) return hipErrorInvalidValue;
-    // at least one workgroup: a dispatch with no work (mm_prepare) still reaches the queue
-    const dim3 g((unsigned)std::max<long long>(a.waves_total, 1)), b(64 * P);
-    (void)hipGetLastError();  // the status below is this launch's, not an earlier call's
-    hipLaunchKernelGGL((mm_wide_kernel<C, NA, KW, P, MW, MM_WIDE_U, MM_WIDE_B, RED, NT>), g, b, 0,
-                       s, a);
-    return hipGetLastError();
+const KernelInst* wide_inst_v() {
+    return inst_of<mm_wide_kernel<C, NA, KW, P, MW, MM_WIDE_U, MM_WIDE_B, RED, NT>, 64 * P>();
 }
 
-// a.seg must be set (segment schedule); variant bit 0: non-temporal stores.
+// the four instances of one shape: non-temporal stores or not, the step sums or not
 template <int C, int NA, int KW, int P, int MW>
-hipError_t wide_launch2(bool red, const PassArgs& a, hipStream_t s, int v) {
-    if (!a.seg) return hipErrorInvalidValue;
-    return (v & 1) ? wide_launch3<C, NA, KW, P, MW, 1>(red, a, s)
-                   : wide_launch3<C, NA, KW, P, MW, 0>(red, a, s);
-}
-
-// Resident workgroups per CU, from the kernel's registers (512 per SIMD lane, granules of
-// 8, at most 8 waves per SIMD) and its LDS (160 KiB per CU); see seg_blocks_per_cu_v.
-template <int C, int NA, int KW, int P, int MW, bool RED, int NT>
-int wide_blocks_v() {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(
-        &fa, reinterpret_cast<const void*>(
-                 mm_wide_kernel<C, NA, KW, P, MW, MM_WIDE_U, MM_WIDE_B, RED, NT>));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return 0;
-    }
-    const int regs = (fa.numRegs + 7) / 8 * 8;
-    const int waves_per_simd = regs > 0 ? std::min(8, 512 / regs) : 8;
-    int blocks = waves_per_simd * 4 / P;
-    if (fa.sharedSizeBytes > 0) blocks = std::min(blocks, (int)(160 * 1024 / fa.sharedSizeBytes));
-    return std::max(blocks, 0);
-}
-
-template <int C, int NA, int KW, int P, int MW>
-int wide_blocks(bool red, int nt) {
-    if (red)
-        return nt ? wide_blocks_v<C, NA, KW, P, MW, true, 1>()
-                  : wide_blocks_v<C, NA, KW, P, MW, true, 0>();
-    return nt ? wide_blocks_v<C, NA, KW, P, MW, false, 1>()
-              : wide_blocks_v<C, NA, KW, P, MW, false, 0>();
+const KernelInst* wide_inst(const InstKey& q) {
+    if (!wide_key<C, NA, KW, P>(q)) return nullptr;
+    if (q.nt)
+        return q.red ? wide_inst_v<C, NA, KW, P, MW, true, 1>()
+                     : wide_inst_v<C, NA, KW, P, MW, false, 1>();
+    return q.red ? wide_inst_v<C, NA, KW, P, MW, true, 0>()
+                 : wide_inst_v<C, NA, KW, P, MW, false, 0>();
 }
 
 }  // namespace

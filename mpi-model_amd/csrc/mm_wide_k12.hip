@@ -4,11 +4,8 @@
 
 namespace mm {
 
-hipError_t wide_launch_k12(bool red, const PassArgs& a, hipStream_t s, int v) {
-    return wide_launch2<4, 1, 3, 4, MM_WIDE_MIN_WAVES>(red, a, s, v);
+const KernelInst* wide_inst_k12(const InstKey& q) {
+    return wide_inst<4, 1, 3, 4, MM_WIDE_MIN_WAVES>(q);
 }
-
-int wide_blocks_k12(bool red, int nt) { return wide_blocks<4, 1, 3, 4, MM_WIDE_MIN_WAVES>(red, nt); }
-
 
 }  // namespace mm

@@ -25,35 +25,21 @@ namespace mm {
 
 #if defined(MM_PART_RED) && defined(MM_PART_NT)
 
-hipError_t MM_PN(wide_launch_k20_r, MM_PART_RED, MM_PART_NT)(const PassArgs& a, hipStream_t s) {
-    return wide_launch4<4, 1, MM_K20_KW, MM_K20_P, MM_WIDE_MIN_WAVES, MM_PART_RED != 0,
-                        MM_PART_NT>(a, s);
-}
-
-int MM_PN(wide_blocks_k20_r, MM_PART_RED, MM_PART_NT)() {
-    return wide_blocks_v<4, 1, MM_K20_KW, MM_K20_P, MM_WIDE_MIN_WAVES, MM_PART_RED != 0,
-                         MM_PART_NT>();
+const KernelInst* MM_PN(wide_inst_k20_r, MM_PART_RED, MM_PART_NT)(const InstKey& q) {
+    if (!wide_key<4, 1, MM_K20_KW, MM_K20_P>(q) || q.red != (MM_PART_RED != 0) ||
+        q.nt != (MM_PART_NT != 0))
+        return nullptr;
+    return wide_inst_v<4, 1, MM_K20_KW, MM_K20_P, MM_WIDE_MIN_WAVES, MM_PART_RED != 0,
+                       MM_PART_NT>();
 }
 
 #else
 
-#define MM_K20_DECL(r, n)                                                                 \
-    hipError_t wide_launch_k20_r##r##_n##n(const PassArgs& a, hipStream_t s);              \
-    int wide_blocks_k20_r##r##_n##n();
-MM_K20_DECL(0, 0)
-MM_K20_DECL(0, 1)
-MM_K20_DECL(1, 0)
-MM_K20_DECL(1, 1)
-#undef MM_K20_DECL
-
-hipError_t wide_launch_k20(bool red, const PassArgs& a, hipStream_t s, int v) {
-    if (red) return (v & 1) ? wide_launch_k20_r1_n1(a, s) : wide_launch_k20_r1_n0(a, s);
-    return (v & 1) ? wide_launch_k20_r0_n1(a, s) : wide_launch_k20_r0_n0(a, s);
-}
-
-int wide_blocks_k20(bool red, int nt) {
-    if (red) return nt ? wide_blocks_k20_r1_n1() : wide_blocks_k20_r1_n0();
-    return nt ? wide_blocks_k20_r0_n1() : wide_blocks_k20_r0_n0();
+const KernelInst* wide_inst_k20(const InstKey& q) {
+    for (InstLookup part : {wide_inst_k20_r0_n0, wide_inst_k20_r0_n1, wide_inst_k20_r1_n0,
+                            wide_inst_k20_r1_n1})
+        if (const KernelInst* i = part(q)) return i;
+    return nullptr;
 }
 
 static_assert(MM_K20_P == kWide20Waves, "mm_geom.hpp: waves per workgroup of the K = 20 instance");

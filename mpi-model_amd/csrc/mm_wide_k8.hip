@@ -27,11 +27,8 @@
 
 namespace mm {
 
-hipError_t wide_launch_k8(bool red, const PassArgs& a, hipStream_t s, int v) {
-    return wide_launch2<4, 1, 2, 4, MM_WIDE_MIN_WAVES>(red, a, s, v);
+const KernelInst* wide_inst_k8(const InstKey& q) {
+    return wide_inst<4, 1, 2, 4, MM_WIDE_MIN_WAVES>(q);
 }
-
-int wide_blocks_k8(bool red, int nt) { return wide_blocks<4, 1, 2, 4, MM_WIDE_MIN_WAVES>(red, nt); }
-
 
 }  // namespace mm

@@ -16,13 +16,7 @@
 
 namespace mm {
 
-hipError_t widea_launch_k4(int na, bool red, const PassArgs& a, hipStream_t s, int v) {
-    if (na == 4) return wide_launch2<2, 4, 1, 4, 2>(red, a, s, v & 1);
-    return hipErrorInvalidValue;
-}
-
-int widea_blocks_k4(int na, bool red, int nt) {
-    return na == 4 ? wide_blocks<2, 4, 1, 4, 2>(red, nt & 1) : 0;
-}
+// any four-attribute pass of K = 4, whatever its chains and diffusing attributes
+const KernelInst* widea_inst_k4(const InstKey& q) { return wide_inst<2, 4, 1, 4, 2>(q); }
 
 }  // namespace mm

@@ -7,8 +7,7 @@
 //
 // Compiled once per instance by the Makefile: MM_ND = N (attributes 0..N-1 diffuse, the
 // others pass through; the engine relabels the attributes so that the diffusing ones come
-// first) and MM_CHAIN_POST = P (the pass has a post-chain), into widea8_launch_nN_pP /
-// widea8_blocks_nN_pP.
+// first) and MM_CHAIN_POST = P (the pass has a post-chain), into the lookup widea8_inst_nN_pP.
 #ifndef MM_ND
 #error "MM_ND (1..4) is set per object by the Makefile"
 #endif
@@ -26,19 +25,16 @@
 #define MM_WIDE_GEN_ROW 0  // per-column GEN weights: the row-factor body spills here (n4 p1: 125 -> 379)
 #include "mm_wide.hpp"
 
-#define MM_CAT3(a, b, c) a##b##c
-#define MM_NAME(f, n, p) MM_CAT3(f, n, p)
-#define MM_LAUNCH MM_NAME(widea8_launch_n, MM_ND, MM_NAME(_p, MM_CHAIN_POST, ))
-#define MM_BLOCKS MM_NAME(widea8_blocks_n, MM_ND, MM_NAME(_p, MM_CHAIN_POST, ))
+#define MM_CAT4(a, b, c, d) a##b##c##d
+#define MM_NAME(f, n, p) MM_CAT4(f, n, _p, p)
 
 namespace mm {
 
-hipError_t MM_LAUNCH(bool red, const PassArgs& a, hipStream_t s) {
-    return wide_launch3<2, 4, 2, 4, 2, 1>(red, a, s);
-}
-
-int MM_BLOCKS(bool red) {
-    return red ? wide_blocks_v<2, 4, 2, 4, 2, true, 1>() : wide_blocks_v<2, 4, 2, 4, 2, false, 1>();
+// (only the non-temporal instances are built: q.nt does not apply)
+const KernelInst* MM_NAME(widea8_inst_n, MM_ND, MM_CHAIN_POST)(const InstKey& q) {
+    if (!wide_key<2, 4, 2, 4>(q) || q.ring || q.nd != MM_ND || q.post != (MM_CHAIN_POST != 0))
+        return nullptr;
+    return q.red ? wide_inst_v<2, 4, 2, 4, 2, true, 1>() : wide_inst_v<2, 4, 2, 4, 2, false, 1>();
 }
 
 }  // namespace mm

@@ -29,15 +29,10 @@
 
 namespace mm {
 
-hipError_t widear_launch_k8(int na, bool red, const PassArgs& a, hipStream_t s, int v) {
-    if (na == 4) return wide_launch2<2, 4, MM_WIDEAR_KW, 8 / MM_WIDEAR_KW, 2>(red, a, s, v);
-    return hipErrorInvalidValue;
+const KernelInst* widear_inst_k8(const InstKey& q) {
+    return q.ring ? wide_inst<2, 4, MM_WIDEAR_KW, 8 / MM_WIDEAR_KW, 2>(q) : nullptr;
 }
 
 static_assert(8 / MM_WIDEAR_KW == kWideRingWaves, "mm_geom.hpp: waves per workgroup of the ring instance");
-
-int widear_blocks_k8(int na, bool red, int nt) {
-    return na == 4 ? wide_blocks<2, 4, MM_WIDEAR_KW, 8 / MM_WIDEAR_KW, 2>(red, nt) : 0;
-}
 
 }  // namespace mm
