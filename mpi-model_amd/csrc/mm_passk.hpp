@@ -160,10 +160,12 @@ __device__ __forceinline__ void proc_n(const PassArgs& A, const Lane& c, long lo
         } else if (inner) {  // interior row, interior strip: cnt == 8, w = u
             w0[a] = u0[a];
             w1[a] = u1[a];
-        } else {  // a column outside the grid (span 0: its pitch padding) weighs 0 by select,
-                  // so no value it holds reaches a cell
-            w0[a] = c.sy0 == 0 ? 0.0 : u0[a] * c8_of(sx * c.sy0 - 1);
-            w1[a] = c.sy1 == 0 ? 0.0 : u1[a] * c8_of(sx * c.sy1 - 1);
+        } else {  // a column outside the grid (span 0: its pitch padding) and a row outside it
+                  // (sx == 0: from level 1 on it holds r/8 times the box sums of the grid's
+                  // first / last row, an infinity where that row has one) weigh 0 by select,
+                  // so no value they hold reaches a cell
+            w0[a] = (sx == 0 || c.sy0 == 0) ? 0.0 : u0[a] * c8_of(sx * c.sy0 - 1);
+            w1[a] = (sx == 0 || c.sy1 == 0) ? 0.0 : u1[a] * c8_of(sx * c.sy1 - 1);
         }
     }
 }

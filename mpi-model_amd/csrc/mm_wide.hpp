@@ -125,18 +125,27 @@ __device__ __forceinline__ void procc(const WLane<C>& c, long long gx, const dou
         w[0] = c.eL ? w0 : w[0];
         w[C - 1] = c.eR ? w1 : w[C - 1];
     } else if (BODY == kBodyGen) {
+        // A row or column outside the grid weighs 0 by select, not by u * 0: from level 1 on
+        // such a cell holds r/8 times the box sum of the grid cells beside it (its own
+        // coefficient is 0), an infinity where one of them is, and inf * 0 is NaN.
         const int sx = span3(c.H, gx);
         if (!MM_WIDE_GEN_ROW || c.gen) {
 #pragma unroll
-            for (int k = 0; k < C; ++k) w[k] = u[k] * c8_of(sx * c.sy[k] - 1);
+            for (int k = 0; k < C; ++k)
+                w[k] = (sx == 0 || c.sy[k] == 0) ? 0.0 : u[k] * c8_of(sx * c.sy[k] - 1);
         } else {
             // 3 * sx - 1 neighbours in an interior column, 2 * sx - 1 in the first / last
+            // (the columns past the grid are kept out at wemit's hand-off); the row's select
+            // has a scalar condition -- a branch here would cut the levels' chains apart
             const double fr = c8_of(3 * sx - 1), fe = c8_of(2 * sx - 1);
             const double w0 = u[0] * fe, w1 = u[C - 1] * fe;
+            double t[C];
 #pragma unroll
-            for (int k = 0; k < C; ++k) w[k] = u[k] * fr;
-            w[0] = c.eL ? w0 : w[0];
-            w[C - 1] = c.eR ? w1 : w[C - 1];
+            for (int k = 0; k < C; ++k) t[k] = u[k] * fr;
+            t[0] = c.eL ? w0 : t[0];
+            t[C - 1] = c.eR ? w1 : t[C - 1];
+#pragma unroll
+            for (int k = 0; k < C; ++k) w[k] = sx == 0 ? 0.0 : t[k];
         }
     }
 }

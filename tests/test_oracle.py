@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import value_classes as vc
 from conftest import golden, golden_points
 
 
@@ -101,9 +102,14 @@ def _contract_step(O, v, rate):
 
 @pytest.mark.parametrize("shape", [(1, 1), (1, 6), (5, 1), (2, 2), (3, 3), (7, 9), (8, 10),
                                    (13, 6)])
-@pytest.mark.parametrize("rate", [0.1, 0.37])
+@pytest.mark.parametrize("rate", [0.1, 0.37] + list(vc.FINITE))
 def test_oracle_step_is_the_written_contract(O, shape, rate):
-    v = O.fill_random(*shape)
+    # a number: fill_random's [1, 2) at that rate; a name: that value class at its own rate
+    # (np.array_equal, not bits: the Fraction fma of _contract_step cannot make a -0)
+    if isinstance(rate, str):
+        v, rate = vc.make(rate, *shape), vc.RATES[rate]
+    else:
+        v = O.fill_random(*shape)
     assert np.array_equal(O.field_step(v, rate), _contract_step(O, v, rate))
 
 
@@ -199,6 +205,59 @@ def test_flip_symmetry_is_exact(O):
     a = O.field_step(v, 0.25, steps=3)
     assert np.array_equal(O.field_step(v[::-1].copy(), 0.25, steps=3), a[::-1])
     assert np.array_equal(O.field_step(v[:, ::-1].copy(), 0.25, steps=3), a[:, ::-1])
+
+
+@pytest.mark.parametrize("cls", ["signed", "wide", "zeros"])
+def test_flip_symmetry_is_exact_on_value_classes(O, cls):
+    # as above with signs, 81 binades and both zeros (rate -0.25 keeps -0 alive): bits
+    v, r = vc.make(cls, 34, 46), vc.RATES[cls]
+    a = O.field_step(v, r, steps=3)
+    vc.assert_same_bits(O.field_step(v[::-1].copy(), r, steps=3), a[::-1], (cls, "rows"))
+    vc.assert_same_bits(O.field_step(v[:, ::-1].copy(), r, steps=3), a[:, ::-1], (cls, "cols"))
+
+
+@pytest.mark.parametrize("cls", ["signed", "wide"])
+def test_conservation_on_value_classes(O, cls):
+    # mixed signs: the total may cancel to nearly nothing, the rounding does not -- the bound
+    # is relative to the sum of the magnitudes
+    v = vc.make(cls, 61, 47)
+    o = O.field_step(v, vc.RATES[cls], steps=20)
+    s0, s1 = math.fsum(v.ravel()), math.fsum(o.ravel())
+    assert abs(s1 - s0) <= 1e-12 * math.fsum(np.abs(v).ravel())
+
+
+def test_value_classes_keep_their_character(O):
+    """What each class is for must still be there after the deepest run the GPU tests make
+    (K = 20 and one more step; two passes of 21 and one more), under the oracle alone: an
+    edit of a generator or of a rate that hollows a class out fails here."""
+    shape = (130, 450)
+    n = shape[0] * shape[1]
+    # 1. both zeros alive after 21 steps at the negative rate
+    z = O.field_step(vc.zeros(*shape), vc.RATES["zeros"], steps=21)
+    neg = int(np.count_nonzero((z == 0.0) & np.signbit(z)))
+    pos = int(np.count_nonzero((z == 0.0) & ~np.signbit(z)))
+    assert neg >= 10000 and pos >= 10000, (neg, pos)
+    # 2. subnormal stays subnormal and never rounds to zero: a flush to zero shows in all cells
+    s = O.field_step(vc.subnormal(*shape), vc.RATES["subnormal"], steps=43)
+    tiny = np.finfo(np.float64).tiny
+    assert int(np.count_nonzero((s != 0.0) & (np.abs(s) < tiny))) == n
+    # 3. the unstable rate of `huge` and the 81 binades of `wide` do not overflow
+    for cls in ("huge", "wide"):
+        o = O.field_step(vc.make(cls, *shape), vc.RATES[cls], steps=43)
+        assert np.all(np.isfinite(o)), cls
+    # 4. a non-finite cell spreads exactly one cell per step, whichever kind it is
+    H, W = 40, 60
+    pos4 = [(0, 0), (H - 1, W - 1), (0, W // 2), (H // 2, 0), (17, 23), (17, 24), (30, 50)]
+    starts = [vc.nonfinite(H, W, 0, pos4)]
+    for kind in vc.NONFINITE_SEEDS:
+        v = vc.signed(H, W)
+        for x, y in pos4:
+            v[x, y] = kind
+        starts.append(v)
+    for v in starts:
+        for steps in (1, 5, 11):
+            o = O.field_step(v, vc.RATES["nonfinite"], steps=steps)
+            assert np.array_equal(~np.isfinite(o), vc.ball_mask((H, W), pos4, steps)), steps
 
 
 @pytest.mark.parametrize("H,G", [(37, 1), (37, 2), (37, 3), (40, 4), (41, 8), (9, 9)])
