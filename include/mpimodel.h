@@ -29,6 +29,9 @@ extern "C" {
 #endif
 
 #define MM_ABI_VERSION 3
+/* Most steps one kernel pass of a rate-field diffusion fuses (mm_fieldk_kernel, K = 2 ..
+ * MM_FIELD_MAX_STEPS; MM_FIELD_STEPS). */
+#define MM_FIELD_MAX_STEPS 4
 
 enum mm_status {
     MM_OK = 0,
@@ -66,7 +69,11 @@ enum mm_flow_kind {
      * that is zero except at chosen cells is a multi-source flow, a constant field the
      * whole-grid flow, a 0/1-scaled field a mask. mm_add_flow ignores b and rate for this
      * kind. Field diffusions run one step per kernel pass in passes of their own
-     * (consecutive ones of distinct attributes share a pass). */
+     * (consecutive ones of distinct attributes share a pass) -- except a program that is
+     * exactly one field diffusion, on a one-attribute engine of a single slab without a
+     * halo (nranks == 1, MM_HALO_NONE): its passes fuse up to MM_FIELD_MAX_STEPS steps on
+     * mm_fieldk_kernel (MM_FIELD_STEPS; by default on slabs of 2^22 cells and more), bit for
+     * bit the same result. */
     MM_FLOW_DIFFUSE_FIELD = 3
 };
 
@@ -106,12 +113,15 @@ typedef struct mm_info {
     int fused_attrs;           /* attributes carried per fused pass */
     int steps_per_launch;      /* steps fused per kernel pass (temporal blocking): 1..10
                                   (mm_passk_kernel), 4/8/12/16/20 (mm_wide_kernel, 4/8 for
-                                  four-attribute programs); mixed plans: mm_pass_plan */
+                                  four-attribute programs), 2..MM_FIELD_MAX_STEPS
+                                  (mm_fieldk_kernel); mixed plans: mm_pass_plan */
     int kernel;                /* step kernel: 0 one step per pass (mm_pass_kernel, or
                                   mm_field_kernel for a rate-field pass),
                                   2 mm_passk_kernel (steps_per_launch steps per pass, all
                                   levels in one wave), 3 mm_wide_kernel (steps_per_launch
-                                  steps per pass, the levels split over 4 waves) */
+                                  steps per pass, the levels split over 4 waves),
+                                  4 mm_fieldk_kernel (steps_per_launch steps of a rate-field
+                                  diffusion per pass; a pass of one step: mm_field_kernel) */
     int halo_depth;            /* ghost rows one border exchange fills (= steps per pass) */
     int graph_state;           /* 0 no graph used yet, 1 steps replayed as hipGraphs,
                                   -1 stream capture refused: steps run eagerly (graph_note) */
@@ -217,7 +227,10 @@ int mm_device_synchronize(int device);
  * kernel's split passes with K-row border segments instead of full-length top / bottom
  * segments), the variable MM_CHAIN_RING set to 0 (four-attribute ring programs on the
  * runtime-operand instance), MM_SYNC_SPIN=0 (mm_synchronize: the blocking wait alone, no
- * polling) and
+ * polling),
+ * MM_FIELD_STEPS (steps per pass of a program that is one rate-field diffusion: 1 one step
+ * per pass, 2..MM_FIELD_MAX_STEPS that K on mm_fieldk_kernel, 0 or unset the default by
+ * slab size; MM_PASSK=0 also means one step per pass there) and
  * MM_KERNEL_VARIANT (non-temporal stores;
  * the four-attribute K = 8 instances always store non-temporal) override tuning;
  * MM_SELF_HALO=1 with MM_HALO_RCCL and nranks == 1 makes the rank
@@ -296,8 +309,10 @@ int mm_prepare(mm_engine* eng, long long nsteps, long long reduce_every);
  * (src/Model.hpp:180-183) is commented out. */
 int mm_pass_plan(mm_engine* eng, long long nsteps, int* lens, int cap, int* count);
 /* The kernel a pass of k steps launches (for rooflines): *kernel 0 = one-step
- * mm_pass_kernel, 2 = mm_passk_kernel, 3 = mm_wide_kernel; *cols_per_lane = columns one
- * lane computes (2 for mm_passk_kernel; 4, or 2 for four-attribute programs, for mm_wide_kernel); *strips = column
+ * mm_pass_kernel / mm_field_kernel, 2 = mm_passk_kernel, 3 = mm_wide_kernel, 4 =
+ * mm_fieldk_kernel (k >= 2 of a K-step rate-field program); *cols_per_lane = columns one
+ * lane computes (2 for mm_passk_kernel and mm_fieldk_kernel; 4, or 2 for four-attribute
+ * programs, for mm_wide_kernel); *strips = column
  * strips of the slab, counted in 64-lane wave columns (a mm_wide_kernel strip of several
  * column waves counts each; 0 for the one-step kernel). */
 int mm_pass_kernel(mm_engine* eng, int k, int* kernel, int* cols_per_lane, long long* strips);
@@ -334,7 +349,8 @@ int mm_debug_fill_padding(mm_engine* eng, double value);
  * number of timed launches, their summed duration (ms) and the average algorithmic
  * bytes one launch moves: 16 B per cell of its rows per attribute (read once, written
  * once), whether the launch advances one step or K; 24 B for an attribute
- * that diffuses by its rate field in that pass (the field is read too). */
+ * that diffuses by its rate field in that pass (the field is read too), again whether the
+ * launch is mm_field_kernel's one step or mm_fieldk_kernel's K. */
 int mm_set_timing(mm_engine* eng, int on);
 int mm_timing(mm_engine* eng, long long* n_launches, double* total_ms, double* bytes_per_launch);
 

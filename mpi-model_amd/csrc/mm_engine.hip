@@ -33,6 +33,8 @@
 #include "mm_inst.hpp"
 #include "mm_plan.hpp"
 
+static_assert(MM_FIELD_MAX_STEPS == mm::kFieldMaxSteps, "include/mpimodel.h: MM_FIELD_MAX_STEPS");
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -258,7 +260,8 @@ bool wring(const mm_engine* e) {
 mm::InstKey inst_key(const mm_engine* e, mm::Kernel kernel, int k, int cols, bool seg, bool red,
                      bool nt) {
     mm::InstKey q{};
-    q.family = kernel == mm::kWide ? mm::kInstWide : mm::kInstPassK;
+    q.family = kernel == mm::kWide ? mm::kInstWide
+                                   : (kernel == mm::kFieldK ? mm::kInstFieldK : mm::kInstPassK);
     q.k = k, q.cols = cols, q.na = e->na;
     q.seg = seg, q.red = red, q.nt = nt;
     if (kernel == mm::kWide && e->na > 1 && e->passes.size() == 1) {
@@ -329,6 +332,13 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     pin.ring = wring(e);
     pin.field = false;
     for (const Pass& q : e->passes) pin.field = pin.field || q.field_mask != 0;
+    // K-step rate-field passes (mm_fieldk_kernel): one attribute, one slab without a halo
+    // (so no self-halo either), and a program that is exactly one field diffusion. Chains
+    // would need K ghost rows of the field and border blocks, further attributes a copy.
+    const bool alone = e->na == 1 && e->d.nranks == 1 && e->d.halo_mode == MM_HALO_NONE &&
+                       !pin.split && p && p->field_mask == 1 && p->diffuse_mask == 0 &&
+                       !pin.chains;
+    pin.field_k = alone ? mm::field_steps_for(pin) : 0;
 }
 
 // Border-row exchange with both neighbours in one RCCL group: the first / last `depth`
@@ -412,7 +422,7 @@ int unsplit_halo(mm_engine* e, int depth) {
 int launch(mm_engine* e, const mm::PassLaunches& pl, bool red, const mm::PassArgs& A, hipStream_t s,
            bool border) {
     const int nt = border ? 0 : e->variant;
-    if (pl.kern.kernel == mm::kWide || pl.kern.kernel == mm::kPassK)
+    if (pl.kern.kernel != mm::kOneStep)  // mm_passk_kernel, mm_wide_kernel, mm_fieldk_kernel
         MM_HIP(mm::launch_kstep(
             inst_key(e, pl.kern.kernel, pl.depth, pl.kern.cols, A.seg != 0, red, nt & 1), A, s));
     else if (A.field_mask)  // a rate-field pass
@@ -430,7 +440,7 @@ void set_launch(mm::PassArgs& A, const mm::Launch& l) {
 }
 
 // One kernel pass over the slab, as mm::pass_launches describes it: k fused steps of the
-// one-pass program p on mm_passk_kernel or mm_wide_kernel (bit j of `mask`: append the sums
+// one-pass program p on mm_passk_kernel, mm_wide_kernel or mm_fieldk_kernel (bit j of `mask`: append the sums
 // after step j+1 of the pass to the history), or pass p of one step on the one-step kernel
 // (mask: append its sums). With a halo the interior rows run beside the exchange (every k
 // steps, k rows deep), the border rows after it on the comm stream. time_it: an event pair
@@ -496,7 +506,7 @@ int enqueue_steps(mm_engine* e, long long first, long long n, long long reduce_e
     long long s = first;
     const long long end = first + n;
     auto red = [&](long long step) { return reduce_every > 0 && step % reduce_every == 0; };
-    if (mm::passk_ok(e->pin)) {
+    if (mm::kstep_ok(e->pin)) {
         for (int k : mm::pass_lengths(e->pin, n)) {
             int mask = 0;
             for (int j = 0; j < k; ++j)
@@ -1098,7 +1108,7 @@ int mm_prepare(mm_engine* e, long long nsteps, long long reduce_every) {
     // kernel keeps a few hundred bytes of scratch per lane in its GEN code: its first
     // dispatch started 172 us after its launch, profiles/r06/hiptrace). No step runs: no
     // buffer is read or written.
-    if (mm::passk_ok(e->pin) && tail > 0) {
+    if (mm::kstep_ok(e->pin) && tail > 0) {
         const int red = reduce_every > 0;  // the instance primed
         for (int k : mm::pass_lengths(e->pin, tail))
             MM_TRY(enqueue_pass(e, e->passes[0], k, red, false, true));

@@ -74,15 +74,6 @@ __device__ __forceinline__ void fload_row(const PassArgs& A, int r, int rmax, un
     }
 }
 
-// share of one emitter with cnt in-grid neighbours (src/Model.hpp:199); in_grid false or
-// cnt == 0: the cell emits nothing, by select
-__device__ __forceinline__ void share_one(double v, double f, bool in_grid, int cnt, double& out,
-                                          double& s) {
-    const bool emits = in_grid && cnt > 0;
-    out = emits ? f * v : 0.0;
-    s = cnt == 8 ? out * 0.125 : (emits ? out / (double)cnt : 0.0);
-}
-
 template <int NA>
 __device__ __forceinline__ void fprocess_row(const PassArgs& A, int r, const FRaw<NA>& raw,
                                              bool fast_cols, int sy0, int sy1, int sye,

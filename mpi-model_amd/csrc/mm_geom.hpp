@@ -37,6 +37,24 @@ inline long long passk_max_rows(int k, long long pitch) {
     return (1LL << 31) / (pitch * 8) - (3 * k + 2 * kSegPrefetch1 + 8);
 }
 
+// mm_fieldk_kernel (mm_fieldk.hpp): fused steps per rate-field pass, K = 2..kFieldMaxSteps
+// (include/mpimodel.h MM_FIELD_MAX_STEPS); its strips are mm_passk_kernel's (passk_out_cols).
+constexpr int kFieldMaxSteps = 4;
+constexpr int kFieldPrefetch = 8;  // rows of v in flight per wave
+// Rows of the rate field a wave holds in registers: kFieldPrefetch rows ahead of level 1
+// and the 2(K-1) rows behind it that the later levels still multiply by, rounded up to a
+// multiple of the prefetch depth (the steady loop is unrolled once around the ring).
+constexpr int field_ring(int k) {
+    return (kFieldPrefetch + 2 * (k - 1) + kFieldPrefetch - 1) / kFieldPrefetch * kFieldPrefetch;
+}
+
+// largest segment (rows) of a K-step rate-field pass: every offset into the state and into
+// the field buffer (a ring ahead of the rows, and the segment rounded up to a whole ring)
+// stays below 2^31
+inline long long fieldk_max_rows(int k, long long pitch) {
+    return (1LL << 31) / (pitch * 8) - (3 * k + 2 * field_ring(k) + 8);
+}
+
 inline bool wide_has(int k, int c, int na) {
     if (na > 1) return na == 4 && c == 2 && (k == 4 || k == 8);
     return c == 4 && (k == 4 || k == 8 || k == 12 || k == 16 || k == 20);

@@ -53,7 +53,8 @@ inline int inst_blocks_per_cu(const KernelInst& k) {
 }
 
 // What selects an instance of the K-step kernels.
-enum InstFamily { kInstPassK, kInstWide };  // mm_passk_kernel, mm_wide_kernel
+// mm_passk_kernel, mm_wide_kernel, mm_fieldk_kernel
+enum InstFamily { kInstPassK, kInstWide, kInstFieldK };
 struct InstKey {
     InstFamily family;
     int k;     // fused steps per pass
@@ -95,6 +96,8 @@ MM_INST_DECL(widea8_inst_n1_p0) MM_INST_DECL(widea8_inst_n1_p1)
 MM_INST_DECL(widea8_inst_n2_p0) MM_INST_DECL(widea8_inst_n2_p1)
 MM_INST_DECL(widea8_inst_n3_p0) MM_INST_DECL(widea8_inst_n3_p1)
 MM_INST_DECL(widea8_inst_n4_p0) MM_INST_DECL(widea8_inst_n4_p1)
+// mm_fieldk_k<K>.hip: the K-step rate-field kernel, one attribute, K = 2..kFieldMaxSteps
+MM_INST_DECL(fieldk_inst_k2) MM_INST_DECL(fieldk_inst_k3) MM_INST_DECL(fieldk_inst_k4)
 #undef MM_INST_DECL
 
 // The instance of a key among all units (mm_kernels_k.hip), nullptr if none builds it.
@@ -106,7 +109,11 @@ const KernelInst* find_inst(const InstKey& q);
 // mm_wide_kernel: one workgroup of wide_waves_per_block(k, c, na, ring) waves per strip
 // segment, segment schedule only (a.seg; a.th / a.th_edge rows per block, a.waves_a /
 // a.waves_total count BLOCKS), a.nstrips = ceil(W / wide_out_cols(k, c)); sums into
-// partials[block][k][na]. hipErrorInvalidValue for a key no unit builds.
+// partials[block][k][na].
+// mm_fieldk_kernel (one attribute, one rate-field diffusion, K 2..kFieldMaxSteps): segment
+// schedule only (a.seg), one row range (a.ra0, a.ra1), a.field[0] the rate field; strips,
+// waves and partials as mm_passk_kernel's.
+// hipErrorInvalidValue for a key no unit builds.
 hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s);
 
 }  // namespace mm

@@ -1,5 +1,6 @@
-// mm_kernels_k.hip -- the K-step kernels' one table of instances (templates: mm_passk.hpp
-// and mm_wide.hpp; instance units with their lookups: mm_passk_k1..10.hip, mm_wide*.hip),
+// mm_kernels_k.hip -- the K-step kernels' one table of instances (templates: mm_passk.hpp,
+// mm_wide.hpp and mm_fieldk.hpp; instance units with their lookups: mm_passk_k1..10.hip,
+// mm_wide*.hip, mm_fieldk_k2..4.hip),
 // their launch, and the fixed-order level-sum finalize kernel.
 #include "mm_wide.hpp"
 
@@ -76,7 +77,7 @@ const KernelInst* find_inst(const InstKey& q) {
         wide_inst_k12,     wide_inst_k16,     wide_inst_k20,     widea_inst_k4,
         widear_inst_k8,    widea8_inst_n1_p0, widea8_inst_n1_p1, widea8_inst_n2_p0,
         widea8_inst_n2_p1, widea8_inst_n3_p0, widea8_inst_n3_p1, widea8_inst_n4_p0,
-        widea8_inst_n4_p1};
+        widea8_inst_n4_p1, fieldk_inst_k2,    fieldk_inst_k3,    fieldk_inst_k4};
     for (InstLookup unit : kUnits)
         if (const KernelInst* inst = unit(q)) return inst;
     return nullptr;
@@ -91,7 +92,10 @@ hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s) {
     if (!inst) return hipErrorInvalidValue;
     // at least one workgroup: a dispatch with no work (mm_prepare) still reaches the queue
     long long blocks = std::max<long long>(a.waves_total, 1);  // mm_wide_kernel: one per segment
-    if (q.family == kInstPassK) {
+    if (q.family == kInstFieldK) {
+        if (!a.field[0] || a.field_mask != 1) return hipErrorInvalidValue;
+        blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
+    } else if (q.family == kInstPassK) {
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
         blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
         if (a.xcd_remap) blocks = (blocks + 7) / 8 * 8;

@@ -39,6 +39,16 @@ __device__ __forceinline__ double m8_of(int cnt) {
                                             : (cnt == 2 ? -12.0 : (cnt == 1 ? -16.0 : 0.0))));
 }
 
+// Rate-field diffusion (mm_field.hip, mm_fieldk.hpp): the share of one emitter with cnt
+// in-grid neighbours (src/Model.hpp:199); in_grid false or cnt == 0: the cell emits
+// nothing, by select
+__device__ __forceinline__ void share_one(double v, double f, bool in_grid, int cnt, double& out,
+                                          double& s) {
+    const bool emits = in_grid && cnt > 0;
+    out = emits ? f * v : 0.0;
+    s = cnt == 8 ? out * 0.125 : (emits ? out / (double)cnt : 0.0);
+}
+
 // The two wave shifts by one lane, in two flavours. update_dpp with a tied `old`: the lanes
 // without a source lane (0 / 63) keep `old` -- the one-step kernels, whose edge lanes carry
 // the column beside the strip there.

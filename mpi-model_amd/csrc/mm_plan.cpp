@@ -47,6 +47,7 @@ const KnobRow kKnobRows[] = {
     {"MM_SYNC_SPIN", 'i', -kAny, kAny, [](Knobs& k, double v) { k.sync_spin = v != 0; }},
     {"MM_SELF_HALO", 'i', -kAny, kAny, [](Knobs& k, double v) { k.self_halo = v != 0; }},
     {"MM_KERNEL_VARIANT", 'i', 0, kAny, [](Knobs& k, double v) { k.variant = (int)std::min(v, 1e9); }},
+    {"MM_FIELD_STEPS", 'i', 0, kFieldMaxSteps, [](Knobs& k, double v) { k.field_steps = (int)v; }},
 };
 
 }  // namespace
@@ -206,6 +207,9 @@ int wide_plan_first(const PlanIn& in, long long n, int kcap) {
 // per-column GEN body: C5 -10 % at full length; profiles/r05/edge).
 double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
     if (in.knobs.seg_edge > 0.0) return in.knobs.seg_edge;
+    // mm_fieldk_kernel: the general body adds a short division per edge cell and keeps the
+    // levels interleaved; full-length edge segments until a measurement says otherwise
+    if (kernel == kFieldK) return 1.0;
     if (kernel == kWide) return in.n_attr == 1 ? 1.0 : 0.5;
     if (k >= 10) return 0.1;
     if (k == 9) return 0.2;
@@ -214,7 +218,27 @@ double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
 
 long long waves_for(long long nstrips, long long n, int th) { return n <= 0 ? 0 : nstrips * ceil_div(n, th); }
 
+bool fieldk_on(const PlanIn& in) { return in.field_k >= 2; }
+
+// MM_FIELD_STEPS unset: K = kFieldAutoSteps on slabs of at least kFieldAutoCells cells
+// (the table of tools/bench_field.py: the built K of the best time per step
+// at 8192^2, and the smallest measured size at which it beat the one-step pass in all three
+// rounds). Never below 2^16 cells: small field grids keep one step per pass.
+constexpr int kFieldAutoSteps = 4;
+constexpr double kFieldAutoCells = 4194304.0;  // 2048^2
+static_assert(kFieldAutoCells >= 65536.0 && kFieldAutoSteps <= kFieldMaxSteps, "auto rule");
+
 }  // namespace
+
+int field_steps_for(const PlanIn& in) {
+    const int k = in.knobs.field_steps;
+    if (!in.knobs.passk || k == 1 || in.pitch <= 0 || fieldk_max_rows(kFieldMaxSteps, in.pitch) < 64)
+        return 0;
+    if (k >= 2) return std::min(k, kFieldMaxSteps);
+    return (double)in.h * (double)in.W >= kFieldAutoCells ? kFieldAutoSteps : 0;
+}
+
+bool kstep_ok(const PlanIn& in) { return fieldk_on(in) || passk_ok(in); }
 
 bool passk_ok(const PlanIn& in) {
     if (!in.knobs.passk || in.n_passes != 1 || in.field) return false;
@@ -224,12 +248,17 @@ bool passk_ok(const PlanIn& in) {
 }
 
 KernelChoice kernel_for(const PlanIn& in, int k) {
+    // a rate-field program in K-step passes: a pass of one step stays on mm_field_kernel
+    if (fieldk_on(in) && k >= 2) return {kFieldK, 2, ceil_div(in.W, passk_out_cols(k))};
     if (!passk_ok(in)) return {kOneStep, 1, 0};  // one mm_pass_kernel launch per pass of the step
     if (use_wide(in, k)) return {kWide, wcols(in), ceil_div(in.W, wide_out_cols(k, wcols(in)))};
     return {kPassK, 2, ceil_div(in.W, passk_out_cols(k))};
 }
 
-int steps_per_launch(const PlanIn& in) { return passk_ok(in) ? passk_steps(in) : 1; }
+int steps_per_launch(const PlanIn& in) {
+    if (fieldk_on(in)) return in.field_k;
+    return passk_ok(in) ? passk_steps(in) : 1;
+}
 
 // Steps of the next K-step pass when n steps remain: ceil(n / K) passes of balanced
 // length (20 steps at K = 8: 7 + 7 + 6, not 8 + 8 + 4), where K is the auto or configured
@@ -238,6 +267,8 @@ int steps_per_launch(const PlanIn& in) { return passk_ok(in) ? passk_steps(in) :
 // the plan of least modelled time: 20 steps run as 10 + 10, a long run stays at K = 8
 // (1000 steps: 125 passes).
 int next_pass_len(const PlanIn& in, long long n) {
+    // a rate-field program: ceil(n / K) balanced passes (7 steps at K = 4: 4 + 3)
+    if (fieldk_on(in)) return (int)ceil_div(n, ceil_div(n, in.field_k));
     if (!passk_ok(in)) return 1;
     const Knobs& kn = in.knobs;
     const int kp = passk_steps(in);
@@ -294,7 +325,8 @@ long long seg_wave_count(long long n, long long ns, long long r, long long re) {
 // every workgroup, one per strip segment) fits seg_waves x the chip's resident slots (the
 // kernel's occupancy x CUs).
 Segments segments(const PlanIn& in, Kernel kernel, int k, int slots, long long n, long long ns) {
-    const long long maxr = std::max<long long>(16, passk_max_rows(k, in.pitch));
+    const long long maxr = std::max<long long>(
+        16, kernel == kFieldK ? fieldk_max_rows(k, in.pitch) : passk_max_rows(k, in.pitch));
     const double edge = seg_edge_of(in, kernel, k);
     const double units = ns < 3 ? (double)ns / edge : (double)(ns - 2) + 2.0 / edge;
     // even segment lengths: with an even first row (x_init and lo even, as every bench
@@ -350,6 +382,7 @@ PassLaunches pass_launches(const PlanIn& in, int k, bool red) {
     const long long h = in.h;
     const int ns = kernel == kOneStep ? (int)(in.pitch / kStripCols) : (int)p.kern.strips;
     p.depth = kernel == kOneStep ? 1 : k;
+    // (a kFieldK pass is never split: field_k is set on slabs without a halo only)
     p.split = in.split && h >= 2 * p.depth + 1;  // else: slab too thin, one launch after the exchange
     auto blocks = [&](long long lo, long long hi, long long lo2, long long hi2, int th) {
         Launch l;
@@ -414,7 +447,7 @@ long long graph_per(const PlanIn& in, long long nsteps, long long reduce_every, 
         return a;
     };
     const long long unit = steps_per_launch(in);
-    const long long flips = passk_ok(in) ? 1 : (long long)in.n_passes;
+    const long long flips = kstep_ok(in) ? 1 : (long long)in.n_passes;  // per unit: one pass
     long long len = unit * ((flips % 2) ? 2 : 1);
     if (reduce_every > 0) len = len / gcd(len, reduce_every) * reduce_every;
     if (len > 256 || nsteps < len || (!in.knobs.graphs_ok && !any)) return 0;
@@ -445,7 +478,8 @@ long long partials_need(const PlanIn& in) {
     // doubles: one-step kernel, 128-column strips x 8-row blocks with kMaxAttr sums per
     // wave (+ 1-row border blocks); mm_passk_kernel, segments of >= 8 rows (edge strips)
     // plus 4-row border blocks (depth <= kGhost rows on each side) with K x NA sums per
-    // wave: K <= kMaxSteps for one attribute, K <= 2 for up to kMaxAttr
+    // wave: K <= kMaxSteps for one attribute, K <= 2 for up to kMaxAttr; mm_fieldk_kernel,
+    // segments of >= 16 rows over no more strips than these, K <= kFieldMaxSteps sums per wave
     const long long ns1 = in.pitch / kStripCols;
     const long long need = (waves_for(ns1, in.h, 8) + 2 * waves_for(ns1, 2, 1) + 16) * kMaxAttr;
     const long long ns = ceil_div(in.W, passk_out_cols(kMaxSteps));

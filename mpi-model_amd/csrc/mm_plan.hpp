@@ -36,11 +36,13 @@ struct Knobs {
                              // (MM_SYNC_SPIN=0: the blocking wait alone)
     bool self_halo = false;  // MM_SELF_HALO: one RCCL rank exchanges border rows with itself
     int variant = -1;        // kernel tuning variant (MM_KERNEL_VARIANT; -1: by buffer size)
+    int field_steps = 0;     // steps per rate-field pass (MM_FIELD_STEPS: 1 one step per pass,
+                             // 2..kFieldMaxSteps that K on mm_fieldk_kernel; 0: auto)
 };
 // `get` is std::getenv or a stand-in for it.
 Knobs read_knobs(const std::function<const char*(const char*)>& get);
 
-enum Kernel { kOneStep = 0, kPassK = 2, kWide = 3 };  // mm_info.kernel's numbers
+enum Kernel { kOneStep = 0, kPassK = 2, kWide = 3, kFieldK = 4 };  // mm_info.kernel's numbers
 
 struct PlanIn {
     long long H = 0, W = 0, h = 0, x_init = 0;
@@ -55,9 +57,12 @@ struct PlanIn {
     bool chains = false;     // pre- or post-chain transfers
     bool ring = false;       // the ring instance runs its K = 8 passes (waves per workgroup)
     bool field = false;      // some pass is a rate-field pass (mm_field_kernel): one step per pass
+    int field_k = 0;         // >= 2: the program is one rate-field diffusion of one attribute on
+                             // a slab without a halo, and its passes fuse up to this many steps
+                             // on mm_fieldk_kernel (the engine sets field_steps_for; 0: off)
     Knobs knobs;
     int ncu = 0;             // compute units of the device
-    // resident wave (kPassK) or workgroup (kWide) slots per CU of the instance that runs a
+    // resident wave (kPassK, kFieldK) or workgroup (kWide) slots per CU of the instance that runs a
     // pass of k steps, with the step sums or without: the one plan input the device gives
     std::function<int(Kernel, int k, bool red)> slots;
 };
@@ -70,7 +75,7 @@ struct KernelChoice {
 
 struct Segments {
     int th, th_edge;   // rows per interior-strip and per edge-strip segment
-    long long count;   // waves (kPassK) or workgroups (kWide)
+    long long count;   // waves (kPassK, kFieldK) or workgroups (kWide)
 };
 
 // One kernel launch: rows [lo, hi) and [lo2, hi2) of the slab, as mm::PassArgs wants them.
@@ -90,10 +95,16 @@ struct PassLaunches {
     long long total;  // partials units of the whole pass
 };
 
-// Can the program run on the K-step kernels? One pass per step (one attribute: a single
+// Can the program run on mm_passk_kernel / mm_wide_kernel? One pass per step (one attribute: a single
 // diffusion; several: diffusions and transfer chains), no rate-field pass, and buffer offsets
 // below 2^31.
 bool passk_ok(const PlanIn& in);
+// Steps per pass of a program that may run on mm_fieldk_kernel (one attribute, one slab, no
+// halo, exactly one rate-field diffusion -- the engine checks that): MM_FIELD_STEPS, or the
+// auto rule by the slab's cells; 0 where it stays one step per pass (also with MM_PASSK=0).
+int field_steps_for(const PlanIn& in);
+// A run advances in K-step passes of the program's only pass: passk_ok, or field_k >= 2.
+bool kstep_ok(const PlanIn& in);
 KernelChoice kernel_for(const PlanIn& in, int k);
 // Steps one kernel pass advances: K with the K-step kernels, 1 otherwise. Also the ghost
 // rows one exchange must fill.

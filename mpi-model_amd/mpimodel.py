@@ -18,6 +18,7 @@ MM_OK = 0
 MM_FLOW_DIFFUSE = 1
 MM_FLOW_TRANSFER = 2
 MM_FLOW_DIFFUSE_FIELD = 3
+FIELD_MAX_STEPS = 4  # MM_FIELD_MAX_STEPS: most steps mm_fieldk_kernel fuses per pass (MM_FIELD_STEPS)
 MM_FILL_UNIFORM = 0
 MM_FILL_RANDOM = 1
 MM_HALO_NONE = 0

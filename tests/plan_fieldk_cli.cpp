@@ -1,0 +1,190 @@
+// plan_fieldk_cli.cpp -- the host-only planner (mpi-model_amd/csrc/mm_plan.cpp) on programs
+// whose rate-field passes fuse K steps (mm::PlanIn::field_k, mm_fieldk_kernel), for
+// tests/test_fieldk_cpu.py. Built with plain g++ (no ROCm headers). Prints one line per
+// failed check and exits 1, else "ok <kFieldMaxSteps>".
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../mpi-model_amd/csrc/mm_plan.hpp"
+
+namespace {
+
+int g_failed = 0;
+
+void expect(bool ok, const char* what, int line) {
+    if (ok) return;
+    std::printf("line %d: %s\n", line, what);
+    g_failed = 1;
+}
+#define EXPECT(c) expect((c), #c, __LINE__)
+
+// Slab g of G of an H x W grid (mm_partition_rows), one attribute, one rate-field pass.
+mm::PlanIn slab(long long H, long long W, int G, int g) {
+    mm::PlanIn in;
+    in.H = H, in.W = W, in.nranks = G;
+    in.x_init = g * H / G;
+    in.h = (g + 1) * H / G - in.x_init;
+    in.min_rows = std::min(in.h, H / G);
+    in.pitch = (W + mm::kStripCols - 1) / mm::kStripCols * mm::kStripCols;
+    in.n_attr = 1, in.n_passes = 1, in.diffuse_mask = 0;
+    in.field = true;
+    in.split = G > 1;
+    in.knobs.th = 8;  // what the engine sets for a program with a rate-field pass
+    in.ncu = 256;
+    in.slots = [](mm::Kernel, int, bool) { return 8; };
+    return in;
+}
+
+mm::Knobs knobs_of(const char* name, const char* value) {
+    return mm::read_knobs([&](const char* n) -> const char* {
+        return std::strcmp(n, name) == 0 ? value : nullptr;
+    });
+}
+
+long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
+
+// field_k = 0: the one-step answers of today, whatever the rest of the input says
+void check_off(const mm::PlanIn& on) {
+    EXPECT(on.field_k == 0);
+    EXPECT(!mm::passk_ok(on) && !mm::kstep_ok(on));
+    EXPECT(mm::steps_per_launch(on) == 1);
+    EXPECT(mm::pass_lengths(on, 7) == std::vector<int>(7, 1));
+    EXPECT(mm::next_pass_len(on, 20) == 1);
+    EXPECT(mm::kernel_for(on, 1).kernel == mm::kOneStep);
+    EXPECT(mm::kernel_for(on, 4).kernel == mm::kOneStep);
+    EXPECT(mm::slab_plan(on).kernel == mm::kOneStep);
+    EXPECT(mm::slab_plan(on).steps_per_launch == 1);
+    for (int red = 0; red < 2; ++red) {
+        const mm::PassLaunches p = mm::pass_launches(on, 1, red);
+        const long long h = on.h, ns = on.pitch / mm::kStripCols;
+        EXPECT(p.kern.kernel == mm::kOneStep && p.depth == 1);
+        EXPECT(p.interior.nstrips == ns && p.interior.th == 8 && p.interior.seg == 0);
+        if (on.split && h >= 3) {
+            EXPECT(p.split && p.interior.lo == 1 && p.interior.hi == h - 1);
+            EXPECT(p.border.th == 1 && p.border.waves_total == 2 * ns);
+        } else {
+            EXPECT(!p.split && p.interior.lo == 0 && p.interior.hi == h);
+        }
+        EXPECT(p.interior.waves_total == ns * ((p.interior.hi - p.interior.lo + 7) / 8));
+        EXPECT(p.total * mm::kMaxAttr <= mm::partials_need(on));
+    }
+    EXPECT(mm::graph_per(on, 64, 0) > 0 && mm::graph_per(on, 64, 0) % 2 == 0);
+}
+
+void check_on(const mm::PlanIn& base, int K) {
+    mm::PlanIn in = base;
+    in.field_k = K;
+    EXPECT(!mm::passk_ok(in) && mm::kstep_ok(in));
+    EXPECT(mm::steps_per_launch(in) == K);
+    for (long long n : {1LL, 7LL, 20LL, 64LL, 1000LL}) {
+        const std::vector<int> lens = mm::pass_lengths(in, n);
+        long long sum = 0;
+        int lo = K, hi = 0;
+        for (int l : lens) {
+            sum += l;
+            lo = std::min(lo, l), hi = std::max(hi, l);
+        }
+        EXPECT(sum == n);
+        EXPECT(hi <= K && lo >= 1 && hi - lo <= 1);
+        EXPECT((long long)lens.size() == ceil_div(n, K));
+        EXPECT(mm::next_pass_len(in, n) == lens[0]);
+    }
+    const mm::KernelChoice one = mm::kernel_for(in, 1);
+    EXPECT(one.kernel == mm::kOneStep && one.cols == 1 && one.strips == 0);
+    for (int k = 2; k <= K; ++k) {
+        const mm::KernelChoice kc = mm::kernel_for(in, k);
+        EXPECT(kc.kernel == mm::kFieldK && kc.cols == 2);
+        EXPECT(kc.strips == ceil_div(in.W, mm::passk_out_cols(k)));
+    }
+    for (int k = 1; k <= K; ++k)
+        for (int red = 0; red < 2; ++red) {
+            const mm::PassLaunches p = mm::pass_launches(in, k, red);
+            EXPECT(!p.split && p.depth == k);
+            EXPECT(p.interior.lo == 0 && p.interior.hi == in.h);
+            EXPECT(p.interior.lo2 == p.interior.hi2 && p.border.waves_total == 0);
+            EXPECT(p.total == p.interior.waves_total && p.interior.partial_base == 0);
+            EXPECT(p.total * mm::kMaxAttr <= mm::partials_need(in));
+            EXPECT(p.total * k <= mm::partials_need(in));
+            if (k == 1) continue;
+            // segments: even, at least 16 rows, offsets into state and field below 2^31, and
+            // the count mm_passk.hpp's seg_map gives for full-length edge segments
+            const mm::Launch& l = p.interior;
+            EXPECT(l.seg == 1 && l.xcd_remap == 0 && l.nstrips == p.kern.strips);
+            EXPECT(l.th >= 16 && l.th % 2 == 0 && l.th_edge == l.th);
+            EXPECT(l.th <= mm::fieldk_max_rows(k, in.pitch));
+            EXPECT((l.th + 3 * k + 2 * mm::field_ring(k)) * in.pitch * 8 < (1LL << 31));
+            EXPECT(l.waves_total == mm::seg_wave_count(in.h, l.nstrips, l.th, l.th_edge));
+            EXPECT(l.waves_total == l.nstrips * ceil_div(in.h, l.th) && l.waves_a == l.waves_total);
+        }
+    const mm::SlabPlan sp = mm::slab_plan(in);
+    EXPECT(sp.kernel == mm::kFieldK && sp.steps_per_launch == K);
+    EXPECT(sp.rows_per_wave == mm::pass_launches(in, K, false).interior.th);
+    EXPECT(sp.waves_per_pass == mm::pass_launches(in, K, false).total);
+    // one flip per pass: a graph of whole K-step passes with an even number of them
+    const long long per = mm::graph_per(in, 64, 0);
+    EXPECT(per > 0 && 64 % per == 0);
+    EXPECT(mm::pass_lengths(in, per).size() % 2 == 0);
+    EXPECT(mm::graph_per(in, 64, 1) > 0);
+}
+
+}  // namespace
+
+int main() {
+    // MM_FIELD_STEPS: 0 / unset auto, 1 off, 2..kFieldMaxSteps that K; anything else is ignored
+    EXPECT(mm::Knobs().field_steps == 0);
+    EXPECT(knobs_of("MM_FIELD_STEPS", "0").field_steps == 0);
+    EXPECT(knobs_of("MM_FIELD_STEPS", "1").field_steps == 1);
+    for (int k = 2; k <= mm::kFieldMaxSteps; ++k)
+        EXPECT(knobs_of("MM_FIELD_STEPS", std::to_string(k).c_str()).field_steps == k);
+    EXPECT(knobs_of("MM_FIELD_STEPS", std::to_string(mm::kFieldMaxSteps + 1).c_str()).field_steps == 0);
+    EXPECT(knobs_of("MM_FIELD_STEPS", "-3").field_steps == 0);
+    EXPECT(knobs_of("MM_STEPS_PER_PASS", "4").field_steps == 0);
+    EXPECT(mm::kFieldMaxSteps >= 4 && mm::kFieldK == 4);
+
+    // field_k = 0 on the shapes of plan_field_cli.cpp: today's one-step plans
+    const long long shapes[][4] = {{512, 512, 1, 0},   {8192, 8192, 1, 0}, {300, 700, 2, 1},
+                                   {77, 300, 4, 2},    {27, 257, 3, 0},    {16, 130, 8, 7},
+                                   {32768, 32768, 8, 3}};
+    for (const auto& s : shapes) {
+        mm::PlanIn on = slab(s[0], s[1], (int)s[2], (int)s[3]);
+        check_off(on);
+        on.knobs.field_steps = 4;  // the knob alone changes no plan: the engine sets field_k
+        check_off(on);
+    }
+
+    // what the engine asks before it sets field_k
+    {
+        mm::PlanIn in = slab(64, 130, 1, 0);
+        EXPECT(mm::field_steps_for(in) == 0);  // auto: small grids keep one step per pass
+        in.h = in.H = 255, in.W = 257;         // 65535 cells: below 2^16 whatever the table says
+        EXPECT(mm::field_steps_for(in) == 0);
+        in = slab(64, 130, 1, 0);
+        for (int k = 2; k <= mm::kFieldMaxSteps; ++k) {
+            in.knobs.field_steps = k;
+            EXPECT(mm::field_steps_for(in) == k);
+        }
+        in.knobs.field_steps = 1;
+        EXPECT(mm::field_steps_for(in) == 0);
+        in.knobs.field_steps = 4;
+        in.knobs.passk = false;  // MM_PASSK=0: one step per kernel pass
+        EXPECT(mm::field_steps_for(in) == 0);
+        mm::PlanIn big = slab(32768, 32768, 1, 0);
+        big.knobs.field_steps = 1;
+        EXPECT(mm::field_steps_for(big) == 0);
+        big.knobs.field_steps = 0;
+        const int k = mm::field_steps_for(big);
+        EXPECT(k == 0 || (k >= 2 && k <= mm::kFieldMaxSteps));
+    }
+
+    const long long grids[][2] = {{512, 512}, {8192, 8192}, {50, 257}, {3, 130}};
+    for (const auto& g : grids)
+        for (int K = 2; K <= mm::kFieldMaxSteps; ++K) check_on(slab(g[0], g[1], 1, 0), K);
+    // a pitch at which the 2^31 offset bound cuts the segments
+    check_on(slab(300000, 5000, 1, 0), mm::kFieldMaxSteps);
+
+    if (!g_failed) std::printf("ok %d\n", mm::kFieldMaxSteps);
+    return g_failed;
+}

@@ -1,0 +1,43 @@
+"""K-step rate-field passes (mm_fieldk_kernel, MM_FIELD_STEPS) without a GPU: the largest K in
+the header and the binding, and the planner's treatment of a program whose rate-field passes
+fuse K steps (tests/plan_fieldk_cli.cpp against mpi-model_amd/csrc/mm_plan.cpp, built with
+plain g++ the way tests/test_ratefield_cpu.py builds its program, and once more under ASan +
+UBSan as a stand-alone program the way tests/test_plan.py builds its own)."""
+import os
+import re
+import subprocess
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRCS = [os.path.join(REPO, "tests", "plan_fieldk_cli.cpp"),
+        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+
+
+def build_and_run(exe, *flags):
+    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *SRCS,
+                        "-o", exe], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-3000:] + r.stderr[-3000:]
+    return int(r.stdout.split()[1])  # the planner's kFieldMaxSteps
+
+
+def header_max_steps():
+    text = open(os.path.join(REPO, "include", "mpimodel.h")).read()
+    m = re.search(r"^#define\s+MM_FIELD_MAX_STEPS\s+(\d+)", text, re.M)
+    assert m, "include/mpimodel.h has no MM_FIELD_MAX_STEPS"
+    assert "MM_FIELD_STEPS" in text.replace("MM_FIELD_MAX_STEPS", "")
+    return int(m.group(1))
+
+
+def test_max_steps_in_header_is_the_bindings(mm):
+    assert header_max_steps() == mm.FIELD_MAX_STEPS >= 4
+
+
+def test_planner_fuses_field_passes(tmp_path):
+    assert build_and_run(str(tmp_path / "plan_fieldk_cli")) == header_max_steps()
+
+
+def test_planner_under_sanitizers(tmp_path):
+    k = build_and_run(str(tmp_path / "plan_fieldk_cli_san"), "-g", "-fsanitize=address,undefined",
+                      "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")
+    assert k == header_max_steps()

@@ -1,14 +1,23 @@
 #!/usr/bin/env python3
-"""Rate-field pass (mm_field_kernel) against the one-step uniform kernel (mm_pass_kernel,
-MM_PASSK=0) on the same grid, in one process: HIP-event time per pass, GCUPS and achieved
-algorithmic bytes/s -- 24 B per cell for the field pass (read v, read f, write v'), 16 B for
-the uniform pass -- as a fraction of the 8 TB/s HBM peak, alternated `--rounds` times.
+"""Rate-field passes on one grid, in one process: the one-step pass (mm_field_kernel,
+MM_FIELD_STEPS=1), the K-step pass for every built K (mm_fieldk_kernel, MM_FIELD_STEPS=K)
+and the one-step uniform kernel (mm_pass_kernel, MM_PASSK=0). HIP-event time per pass and
+per step, GCUPS, algorithmic bytes per cell-update (24 / K for a field pass: read v, read f,
+write v' once per K steps; 16 for the uniform pass) and the achieved algorithmic bytes/s of
+a launch, as a fraction of the 8 TB/s HBM peak; the arms alternate `--rounds` times.
 Needs a GPU; nothing here falls back.
 
-  python tools/bench_field.py [--size 8192] [--warmup 20] [--steps 200] [--rounds 3]
+  python tools/bench_field.py [--sizes 2048,4096,8192,16384] [--warmup 20] [--steps 200]
+                              [--rounds 3]
 
-Prints one JSON line per arm and round, then a summary line: bytes_ratio is the field pass's
-bytes/s over the uniform pass's (target: >= 0.9).
+Every arm times at least --steps steps, rounded up to a multiple of its K. Prints one JSON
+line per arm and round, then per size a summary line. For the K arms the summary holds the
+model of DESIGN.md 4.1 -- 24/K * 128/out_cols(K) B per cell-update moved at the one-step
+field pass's measured bytes/s -- and the share of it the kernel reached; bytes_ratio is the
+one-step field pass's bytes/s over the uniform pass's (target: >= 0.9). The last line
+derives the auto rule of MM_FIELD_STEPS from the table: the K of the best time per step at
+8192^2 (the largest size, if 8192 was not run) and the smallest size at which that K beat
+the one-step pass in every round.
 """
 import argparse
 import json
@@ -21,30 +30,42 @@ import mpimodel as mm  # noqa: E402
 
 mm.lib()
 PEAK = 8e12  # B/s, MI355X HBM3E
+KS = list(range(2, mm.FIELD_MAX_STEPS + 1))
 
 
-def engine(H, W, field):
-    old = os.environ.get("MM_PASSK")
-    os.environ["MM_PASSK"] = "0"  # the uniform arm: one step per pass; the field arm is anyway
+def out_cols(k):
+    return 128 - 4 * ((k + 1) // 2)
+
+
+def engine(H, W, k):
+    """k = 0: the uniform one-step arm; 1: the one-step field pass; >= 2: the K-step pass."""
+    env = {"MM_PASSK": "0"} if k == 0 else {"MM_FIELD_STEPS": str(k)}
+    old = {name: os.environ.get(name) for name in ("MM_PASSK", "MM_FIELD_STEPS")}
+    for name in old:
+        os.environ.pop(name, None)
+    os.environ.update(env)
     try:
         e = mm.Engine(H, W)
     finally:
-        if old is None:
-            os.environ.pop("MM_PASSK", None)
-        else:
-            os.environ["MM_PASSK"] = old
+        for name, v in old.items():
+            os.environ.pop(name, None)
+            if v is not None:
+                os.environ[name] = v
     e.fill_random(0)
-    if field:
+    if k:
         e.rate_field_fill(0.1)
         e.add_diffuse_field(0)
     else:
         e.add_diffuse(0, 0.1)
     info = e.info()
-    assert info["kernel"] == 0 and info["steps_per_launch"] == 1, info
+    want = (4, k) if k >= 2 else (0, 1)
+    assert (info["kernel"], info["steps_per_launch"]) == want, info
     return e
 
 
-def measure(e, cells, warmup, steps):
+def measure(e, cells, k, warmup, steps):
+    k = max(k, 1)
+    steps = -(-steps // k) * k
     e.set_timing(False)
     e.run(warmup)
     e.synchronize()
@@ -53,47 +74,74 @@ def measure(e, cells, warmup, steps):
     e.synchronize()
     n, ms, nbytes = e.timing()
     e.set_timing(False)
-    assert n == steps, (n, steps)
+    assert n == steps // k, (n, steps, k)
     us = ms / n * 1e3
     bps = nbytes / (us * 1e-6)
-    return {"pass_us": round(us, 2), "GCUPS": round(cells / us / 1e3, 1),
-            "bytes_per_cell": round(nbytes / cells, 1), "TBps": round(bps / 1e12, 3),
+    return {"steps": steps, "pass_us": round(us, 2), "step_us": round(us / k, 2),
+            "GCUPS": round(cells * k / us / 1e3, 1),
+            "bytes_per_cell_update": round(nbytes / cells / k, 2), "TBps": round(bps / 1e12, 3),
             "of_peak": round(bps / PEAK, 3)}
+
+
+def span(rows, key):
+    v = [r[key] for r in rows]
+    return {"min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3)}
+
+
+def run_size(size, a):
+    H = W = size
+    arms = {"field": 1, **{"field%d" % k: k for k in KS}, "uniform": 0}
+    engines = {name: engine(H, W, k) for name, k in arms.items()}
+    res = {name: [] for name in arms}
+    for rnd in range(a.rounds):
+        for name, e in engines.items():
+            r = measure(e, H * W, arms[name], a.warmup, a.steps)
+            res[name].append(r)
+            print(json.dumps({"arm": name, "round": rnd, "H": H, "W": W, **r}), flush=True)
+    for e in engines.values():
+        e.close()
+
+    ratios = [f["TBps"] / u["TBps"] for f, u in zip(res["field"], res["uniform"])]
+    out = {"summary": "rate-field passes", "H": H, "W": W, "rounds": a.rounds,
+           "bytes_ratio": {"min": round(min(ratios), 3), "max": round(max(ratios), 3),
+                           "mean": round(sum(ratios) / len(ratios), 3)},
+           "target_met": min(ratios) >= 0.9, "arms": {}}
+    for name, rows in res.items():
+        out["arms"][name] = {key: span(rows, key) for key in
+                             ("pass_us", "step_us", "GCUPS", "bytes_per_cell_update", "TBps", "of_peak")}
+    bps1 = out["arms"]["field"]["TBps"]["mean"] * 1e12
+    for k in KS:
+        arm = out["arms"]["field%d" % k]
+        model_bytes = 24.0 / k * 128.0 / out_cols(k)
+        model_us = H * W * model_bytes / bps1 * 1e6
+        arm["model_bytes_per_cell_update"] = round(model_bytes, 3)
+        arm["model_step_us"] = round(model_us, 2)
+        arm["share_of_model"] = round(model_us / arm["step_us"]["mean"], 3)
+        arm["speedup"] = round(out["arms"]["field"]["step_us"]["mean"] / arm["step_us"]["mean"], 3)
+        # faster than the one-step pass of the same round, in every round
+        arm["beats_one_step"] = all(r["step_us"] < f["step_us"]
+                                    for r, f in zip(res["field%d" % k], res["field"]))
+    print(json.dumps(out), flush=True)
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--size", type=int, default=8192)
+    ap.add_argument("--sizes", default="2048,4096,8192,16384")
+    ap.add_argument("--size", type=int, default=0, help="one size (instead of --sizes)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
-    H = W = a.size
-    arms = {"field": engine(H, W, True), "uniform": engine(H, W, False)}
-    res = {k: [] for k in arms}
-    for rnd in range(a.rounds):
-        for name, e in arms.items():
-            r = measure(e, H * W, a.warmup, a.steps)
-            res[name].append(r)
-            print(json.dumps({"arm": name, "round": rnd, "H": H, "W": W, **r}), flush=True)
-    for e in arms.values():
-        e.close()
+    sizes = [a.size] if a.size else [int(s) for s in a.sizes.split(",")]
+    table = {size: run_size(size, a) for size in sizes}
 
-    def span(name, key):
-        v = [r[key] for r in res[name]]
-        return {"min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3)}
-
-    ratios = [f["TBps"] / u["TBps"] for f, u in zip(res["field"], res["uniform"])]
-    print(json.dumps({"summary": "field vs uniform one-step pass", "H": H, "W": W,
-                      "steps": a.steps, "rounds": a.rounds,
-                      "field_pass_us": span("field", "pass_us"),
-                      "uniform_pass_us": span("uniform", "pass_us"),
-                      "field_TBps": span("field", "TBps"), "uniform_TBps": span("uniform", "TBps"),
-                      "field_of_peak": span("field", "of_peak"),
-                      "uniform_of_peak": span("uniform", "of_peak"),
-                      "bytes_ratio": {"min": round(min(ratios), 3), "max": round(max(ratios), 3),
-                                      "mean": round(sum(ratios) / len(ratios), 3)},
-                      "target_met": min(ratios) >= 0.9}), flush=True)
+    ref = 8192 if 8192 in table else max(table)
+    best = min(KS, key=lambda k: table[ref]["arms"]["field%d" % k]["step_us"]["mean"])
+    wins = [s for s in sorted(table) if table[s]["arms"]["field%d" % best]["beats_one_step"]]
+    print(json.dumps({"auto_rule": "MM_FIELD_STEPS unset", "reference_size": ref, "K": best,
+                      "threshold_cells": max(wins[0] * wins[0], 1 << 16) if wins else None,
+                      "sizes_won": wins}), flush=True)
 
 
 if __name__ == "__main__":
