@@ -6,6 +6,7 @@
 //        swpc: mm_info.seg_waves_per_cu of the device (waves; a wide workgroup's slots x
 //        its waves), handed to the planner as the slots of every instance
 //   plan n | kern k | info | graph nsteps reduce_every any | launch k red
+//   cap k                            passk_max_rows(k, pitch), the same spelled out, the even cut
 //   seg kernel k slots n0 n1 ns      segments() alone for n = n0..n1 rows: th th_edge count cap
 #include <algorithm>
 #include <cstdio>
@@ -76,6 +77,14 @@ int main() {
                 std::printf("%d %d %lld %lld\n", s.th, s.th_edge, s.count,
                             std::max<long long>(16, mm::passk_max_rows(k, in.pitch)));
             }
+        } else if (cmd == "cap") {
+            // the 2^31 offset cap of a k-step segment at this pitch, as the header states it
+            // and spelled out, and the even length segments() cuts a capped segment to
+            int k;
+            is >> k;
+            const long long cap = mm::passk_max_rows(k, in.pitch);
+            std::printf("%lld %lld %lld\n", cap,
+                        (1LL << 31) / (in.pitch * 8) - (3 * k + 2 * mm::kSegPrefetch1 + 8), cap & ~1LL);
         } else if (cmd == "launch") {
             int k, red;
             is >> k >> red;

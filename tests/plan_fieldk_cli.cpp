@@ -182,8 +182,68 @@ int main() {
     const long long grids[][2] = {{512, 512}, {8192, 8192}, {50, 257}, {3, 130}};
     for (const auto& g : grids)
         for (int K = 2; K <= mm::kFieldMaxSteps; ++K) check_on(slab(g[0], g[1], 1, 0), K);
-    // a pitch at which the 2^31 offset bound cuts the segments
-    check_on(slab(300000, 5000, 1, 0), mm::kFieldMaxSteps);
+    // a tall, narrow grid: the occupancy plan's segments stay far below the 2^31 offset cap
+    {
+        mm::PlanIn in = slab(300000, 5000, 1, 0);
+        check_on(in, mm::kFieldMaxSteps);
+        in.field_k = mm::kFieldMaxSteps;
+        const int th = mm::pass_launches(in, in.field_k, false).interior.th;
+        EXPECT(th >= 16 && th < mm::fieldk_max_rows(in.field_k, in.pitch) / 4);
+    }
+    // where the cap binds: 65536^2 under the default knobs, and the grid of
+    // tests/test_gpu_field_large.py (8200 x 32768, MM_SEG_WAVES=0.001: one segment of the cap
+    // and the rest per strip)
+    for (int K = 2; K <= mm::kFieldMaxSteps; ++K) {
+        mm::PlanIn big = slab(65536, 65536, 1, 0);
+        mm::PlanIn cap = slab(8200, 32768, 1, 0);
+        cap.knobs = knobs_of("MM_SEG_WAVES", "0.001");
+        cap.knobs.th = 8;
+        for (mm::PlanIn* in : {&big, &cap}) {
+            check_on(*in, K);
+            in->field_k = K;
+            for (int k = 2; k <= K; ++k)
+                for (int red = 0; red < 2; ++red) {
+                    const long long maxr = mm::fieldk_max_rows(k, in->pitch);
+                    const mm::Launch l = mm::pass_launches(*in, k, red).interior;
+                    EXPECT(l.th == (maxr & ~1LL) && l.th_edge == l.th);
+                    EXPECT(maxr == (1LL << 31) / (in->pitch * 8) - (3 * k + 2 * mm::field_ring(k) + 8));
+                    EXPECT(l.waves_total == l.nstrips * ceil_div(in->h, l.th));
+                }
+            EXPECT(mm::slab_plan(*in).rows_per_wave == (mm::fieldk_max_rows(K, in->pitch) & ~1LL));
+        }
+        // 8200 rows: two segments per strip, the second of 8200 - cap rows ends at the last row
+        const long long th = mm::slab_plan(cap).rows_per_wave;
+        EXPECT(th < 8200 && 8200 - th >= 16 && 8200 - th <= 92 && ceil_div(8200, th) == 2);
+    }
+    EXPECT(mm::fieldk_max_rows(4, 32768) == 8140 && mm::fieldk_max_rows(2, 32768) == 8146);
+    EXPECT(mm::fieldk_max_rows(4, 65536) == 4044);
+
+    // the auto rule and the non-temporal-store rule at the shapes the GPU tests rely on
+    {
+        mm::PlanIn in = slab(2048, 2048, 1, 0);
+        EXPECT(mm::field_steps_for(in) == 4 && mm::kernel_variant(in) == 0);
+        EXPECT(mm::field_steps_for(slab(2047, 2048, 1, 0)) == 0);
+        EXPECT(mm::kernel_variant(slab(4096, 4096, 1, 0)) == 0);  // exactly 256 MiB: not above
+        in = slab(4104, 4096, 1, 0);
+        EXPECT(mm::field_steps_for(in) == 4 && mm::kernel_variant(in) == 1);
+        // the plans of those two grids with 8 slots per CU: 16-row segments in 18 strips,
+        // 36-row segments in 35 strips (114 segment rows)
+        in.field_k = 4;
+        mm::Launch l = mm::pass_launches(in, 4, false).interior;
+        EXPECT(l.th == 36 && l.nstrips == 35 && ceil_div(in.h, l.th) == 114);
+        EXPECT(mm::pass_lengths(in, 7) == (std::vector<int>{4, 3}));
+        in = slab(2048, 2048, 1, 0);
+        in.field_k = 4;
+        l = mm::pass_launches(in, 4, false).interior;
+        EXPECT(l.th == 16 && l.nstrips == 18);
+        EXPECT(mm::pass_lengths(in, 7) == (std::vector<int>{4, 3}));
+        // MM_KERNEL_VARIANT overrides the size rule both ways
+        in.knobs = knobs_of("MM_KERNEL_VARIANT", "1");
+        EXPECT(mm::kernel_variant(in) == 1);
+        in = slab(4104, 4096, 1, 0);
+        in.knobs = knobs_of("MM_KERNEL_VARIANT", "0");
+        EXPECT(mm::kernel_variant(in) == 0);
+    }
 
     if (!g_failed) std::printf("ok %d\n", mm::kFieldMaxSteps);
     return g_failed;

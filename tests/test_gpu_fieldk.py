@@ -209,6 +209,49 @@ def test_reuploaded_field_takes_effect(gpu, O, monkeypatch):
     assert np.array_equal(got, want)
 
 
+@pytest.mark.parametrize("K", [4, 3])
+def test_odd_flip_graph_replays(gpu, O, monkeypatch, K):
+    """run(3K) is three passes: one graph with an odd number of buffer flips, so its three
+    replays start from alternating buffer parities; run(K) after them is an eager pass. The
+    state after every call against the oracle and against an engine that never captures, with
+    another field uploaded between the second and the third replay."""
+    H, W = 64, 130
+    calls = [3 * K, 3 * K, 3 * K, K, K]
+    f1, f2, cnt = random_field(H, W), random_field(H, W, seed=99), neighbour_counts(H, W)
+    want, v = [], O.fill_random(H, W)
+    for i, n in enumerate(calls):
+        for _ in range(n):
+            v = oracle_step(O, v, f2 if i >= 2 else f1, cnt)
+        want.append(v)
+    assert np.array_equal(want[1], reference(O, H, W, 6 * K))
+    got = {}
+    for graphs in (1, 0):
+        env = {} if graphs else {"MM_GRAPH": 0}
+        with fk_engine(gpu, O, monkeypatch, H, W, K, **env) as e:
+            check_fieldk_plan(e, W, K)
+            assert e.pass_plan(3 * K) == [K] * 3 and e.pass_plan(K) == [K]
+            done = 0
+            for i, n in enumerate(calls):
+                if i == 2:
+                    e.rate_field_upload(f2)
+                e.run(n)
+                done += n
+                got[graphs, i] = e.download()
+                info = e.info()
+                assert info["steps_done"] == done, (graphs, i, info)
+                if i == 0:
+                    assert info["graph_state"] == graphs, info
+                    if graphs:
+                        assert info["graph_launches"] == 1, info
+                if i == 2 and graphs:  # one captured graph per buffer parity, replayed
+                    assert info["graph_launches"] == 3 and info["graph_count"] == 2, info
+            if not graphs:
+                assert info["graph_state"] == 0 and info["graph_launches"] == 0, info
+    for i in range(len(calls)):
+        assert np.array_equal(got[1, i], want[i]), (K, i)
+        assert got[1, i].tobytes() == got[0, i].tobytes(), (K, i)
+
+
 # ---- 7. where it must not run -----------------------------------------------------------------
 def one_step(e):
     info = e.info()

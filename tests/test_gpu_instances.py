@@ -3,15 +3,19 @@
 One case per descriptor family: mm_passk_kernel K = 1..10 and mm_wide_kernel K = 4..20 (one
 attribute), the four-attribute mm_wide_kernel instances (K = 4; K = 8 with N = 1..4 diffusing
 attributes, with and without a post-chain; the ring instance and its run-time-chain stand-in),
-and the border launches of a halo-split slab. Every case runs with the step sums off and on
+the border launches of a halo-split slab, and the rate-field family (mm_field_kernel and
+mm_fieldk_kernel K = 2..4, against or_field_step_general). Every case runs with the step sums off and on
 and with MM_KERNEL_VARIANT 0 and 1 (non-temporal stores), and checks through mm_pass_kernel /
 mm_engine_info that the intended kernel, K and columns per lane are the ones planned, so a
 silent fall-back to another instance fails it.
 """
+import math
+
 import pytest
 
 import numpy as np
 
+import test_gpu_ratefield as ratefield
 from test_gpu_halo import close, gather, make_chain, run_chain
 from test_gpu_parity import C5_FLOWS, WIDE_PROGRAMS, add_flows
 
@@ -145,6 +149,55 @@ def test_widea_ring_instance(gpu, O, monkeypatch, ring):
     # MM_CHAIN_RING=0 the run-time-chain instance of four diffusing attributes, no post-chain
     run_case(gpu, O, monkeypatch, FOUR, 4, C5_FLOWS, {"MM_WIDE": 1, "MM_CHAIN_RING": ring},
              WIDE, 8, 2, gpu.MM_CHAIN_RING if ring else gpu.MM_CHAIN_RUNTIME)
+
+
+# ---- the rate-field family: mm_field_kernel and mm_fieldk_kernel K = 2..FIELD_MAX_STEPS --------
+FIELD = (50, 257)  # with SEG: four 16-row segments, an interior strip between two edge strips
+FIELD_KS = (1, 2, 3, 4)  # MM_FIELD_STEPS: 1 is mm_field_kernel, the others mm_fieldk_kernel<K>
+
+
+def run_field_case(gpu, O, monkeypatch, k):
+    """run_case for a one-attribute rate-field diffusion: state fill_random, rates
+    random_field, one pass of K and one more step, against or_field_step_general iterated."""
+    import test_gpu_fieldk as fieldk  # (imports this module through test_gpu_values)
+    H, W = FIELD
+    steps = k + 1
+    for variant in (0, 1):
+        for reduce_every in (0, 1):
+            with fieldk.fk_engine(gpu, O, monkeypatch, H, W, k, **SEG,
+                                  MM_KERNEL_VARIANT=variant) as e:
+                info = e.info()
+                if k == 1:
+                    assert (info["kernel"], info["steps_per_launch"], info["halo_depth"]) == (0, 1, 1)
+                    assert e.pass_kernel(1)[0] == 0 and info["pitch"] == 3 * 128
+                else:
+                    fieldk.check_fieldk_plan(e, W, k)
+                    assert W > 2 * fieldk.out_cols(k)  # an interior strip
+                assert info["rows_per_wave"] * 3 <= H, info  # several segments, one interior
+                assert e.pass_plan(k) == [k] and e.pass_plan(1) == [1]
+                e.run(k, reduce_every)
+                e.run(1, reduce_every)
+                got = e.download()
+                hist = e.sums_history()
+            what = (k, variant, reduce_every)
+            assert np.array_equal(got, ratefield.reference(O, H, W, steps)), what
+            if reduce_every:
+                assert hist.shape == (steps, 1), what
+                for s in range(1, steps + 1):
+                    w = math.fsum(ratefield.reference(O, H, W, s).ravel())
+                    assert abs(hist[s - 1, 0] - w) <= 1e-12 * abs(w), (what, s)
+
+
+@pytest.mark.parametrize("k", FIELD_KS)
+def test_field_instance(gpu, O, monkeypatch, k):
+    run_field_case(gpu, O, monkeypatch, k)
+
+
+def test_every_built_field_k_is_tested(gpu):
+    # a K = 5 instance added to mm_fieldk_kernel must be added to FIELD_KS
+    import test_gpu_fieldk as fieldk
+    assert list(FIELD_KS) == list(range(1, gpu.FIELD_MAX_STEPS + 1))
+    assert list(fieldk.built_ks(gpu)) == list(FIELD_KS[1:])
 
 
 @pytest.mark.parametrize("kernel,k", [(PASSK, 5), (WIDE, 8)])

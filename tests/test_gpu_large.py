@@ -7,9 +7,11 @@ The whole grid is far too big for the oracle, so parity is pinned by
   * three 64-row bands -- the top edge, the rows around an interior segment boundary of
     the K-step kernel's wave plan, the bottom edge -- compared BIT-EXACTLY with the
     oracle run on the band widened by the 8-row dependency cone of 8 steps (every column,
-    so every strip boundary and both edge strips are covered). At pitch 32768 these rows
-    sit at buffer offsets up to ~2^31 from a wave's descriptor base: exactly the
-    large-offset indexing (passk_max_rows, num_records) a small grid never reaches;
+    so every strip boundary and both edge strips are covered). At pitch 32768 these
+    plans' segments are about 2500 rows, so the rows sit at buffer offsets up to ~2^29.3
+    from a wave's descriptor base: large-offset indexing a small grid never reaches, but
+    a third of the cap (passk_max_rows, about 8100 rows there). Segments of exactly the
+    cap are in tests/test_gpu_field_large.py;
   * conservation of the total (1e-12 relative);
   * exact mirror symmetry: the step commutes with flipping both axes.
 """

@@ -205,6 +205,28 @@ def test_segment_plans(cli, na, kernel, ks, seg_waves):
     assert np.all((count <= want) | (th == (maxr & ~1)))
 
 
+def test_segments_at_the_offset_cap(cli):
+    """Where passk_max_rows binds: the grid of tests/test_gpu_field_large.py (8200 x 32768 with
+    MM_SEG_WAVES=0.001: per strip one segment of the cap and the rest) and 65536^2 under the
+    default knobs. The cap is (2^31 / row bytes) less 3K + 2 * kSegPrefetch1 + 8 rows, cut to
+    an even length."""
+    tiny = {"MM_SEG_WAVES": 0.001}
+    cases = [(8200, {**tiny, "MM_WIDE": 0, "MM_STEPS_PER_PASS": 10}, 2, 10, 8138),
+             (8200, {**tiny, "MM_WIDE": 1, "MM_STEPS_PER_PASS": 20}, 3, 20, 8108),
+             (65536, {}, 3, 20, 4012), (65536, {"MM_WIDE": 0}, 2, 8, 4048)]
+    for H, env, kernel, k, want in cases:
+        W = 32768 if H == 8200 else H
+        info, cap, l0, l1 = ask(cli, slab_lines(H, W, env=env) +
+                                ["info", f"cap {k}", f"launch {k} 0", f"launch {k} 1"])
+        assert cap == [want, (1 << 31) // (W * 8) - (3 * k + 2 * 8 + 8), want & ~1], (H, env)
+        assert info[:3] == [kernel, k, want & ~1], (H, env, info)
+        for l in (l0, l1):
+            assert (l[0], l[3], l[4], l[5]) == (kernel, 0, H, want & ~1), (H, env, l)
+            assert 8 <= l[6] <= l[5]
+        if H == 8200:  # two segments per interior strip, the second ends at the last row
+            assert 16 <= H - info[2] <= 92
+
+
 @pytest.mark.parametrize("env,ks", [({"MM_PASSK": 0}, (1,)), ({"MM_WIDE": 0}, PASSK_K),
                                     ({"MM_WIDE": 1}, tuple(range(1, 21))),
                                     ({"MM_WIDE": 1, "MM_BORDER_SEGMENTS": 0}, WIDE_K)],
