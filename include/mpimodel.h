@@ -254,7 +254,15 @@ int mm_download(mm_engine* eng, int attr, double* host);
 /* Flow program. src/Model.hpp:23-27 stores one Flow; the engine keeps an ordered list.
  * One step applies the flows in order; the engine groups them into kernel passes (a
  * diffusion per attribute with up to 4 same-cell transfers before and after it; longer
- * chains start a new pass), which changes no result. */
+ * chains start a new pass), which changes no result.
+ * Both calls may come at any time in an engine's life, between runs included; neither
+ * touches the cells, the rate fields, steps_done or the history. The program is the only
+ * thing they leave behind: after either call the engine plans as a fresh engine of the same
+ * mm_desc and creation environment does once it is given the same flow list -- the same
+ * kernel, steps_per_launch, halo_depth, n_passes, rows_per_wave, waves_per_pass,
+ * fused_attrs, chain_kernel and seg_waves_per_cu in mm_info, the same mm_pass_plan and
+ * mm_pass_kernel -- and runs compute what that engine computes from the same state
+ * (tests/test_gpu_lifetime.py). A refused mm_add_flow changes nothing. */
 int mm_clear_flows(mm_engine* eng);
 int mm_add_flow(mm_engine* eng, int kind, int a, int b, double rate);
 

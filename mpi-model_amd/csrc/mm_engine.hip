@@ -109,6 +109,8 @@ struct mm_engine {
 
     mm::PlanIn pin;  // what the planner sees of the engine (mm_plan.hpp): slab, program shape,
                      // the MM_* knobs, the device; pin.split: interior / border split
+    int th_env = 8;  // MM_ROWS_PER_WAVE as the environment asked; pin.knobs.th is the
+                     // effective height, derived from it and the program (sync_program)
     std::map<const mm::KernelInst*, int> slots;  // occupancy cache (slots_per_cu)
     bool self_halo = false;  // test mode: one RCCL rank exchanges border rows with itself
     int variant = 0;  // kernel tuning variant (MM_KERNEL_VARIANT), 0 = default
@@ -332,6 +334,13 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     pin.ring = wring(e);
     pin.field = false;
     for (const Pass& q : e->passes) pin.field = pin.field || q.field_mask != 0;
+    // transfers, several attributes or a rate field: those kernels exist for 8-row blocks
+    // only. Any other program, the empty one included, gets the height the environment asked
+    // for back: a reprogrammed engine plans as a fresh one (include/mpimodel.h, mm_clear_flows)
+    bool eight = e->na > 1;
+    for (const Pass& q : e->passes)
+        eight = eight || !q.pre.empty() || !q.post.empty() || q.field_mask != 0;
+    pin.knobs.th = eight ? 8 : e->th_env;
     // K-step rate-field passes (mm_fieldk_kernel): one attribute, one slab without a halo
     // (so no self-halo either), and a program that is exactly one field diffusion. Chains
     // would need K ghost rows of the field and border blocks, further attributes a copy.
@@ -742,6 +751,7 @@ int mm_engine_create(const mm_desc* desc, mm_engine** out) {
     // (RCCL engines replace this with the chain's true minimum below)
     pin.min_rows = std::min<long long>(d.h, d.H / d.nranks);
     pin.knobs = mm::read_knobs([](const char* name) -> const char* { return std::getenv(name); });
+    e->th_env = pin.knobs.th;
     pin.slots = [e](mm::Kernel kernel, int k, bool red) { return slots_per_cu(e, kernel, k, red); };
     e->variant = mm::kernel_variant(pin);
 
@@ -946,11 +956,6 @@ int mm_add_flow(mm_engine* e, int kind, int a, int b, double rate) {
     e->flows.push_back({kind, a, kind == MM_FLOW_TRANSFER ? (b < 0 ? -1 : b) : a, rate});
     drop_graphs(e);
     MM_TRY(compile_passes(e));
-    // transfers, several attributes or a rate field: those kernels exist for 8-row blocks only
-    bool chains = e->na > 1;
-    for (const Pass& p : e->passes)
-        chains = chains || !p.pre.empty() || !p.post.empty() || p.field_mask != 0;
-    if (chains) e->pin.knobs.th = 8;
     sync_program(e);
     return MM_OK;
 }
