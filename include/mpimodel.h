@@ -70,10 +70,13 @@ enum mm_flow_kind {
      * whole-grid flow, a 0/1-scaled field a mask. mm_add_flow ignores b and rate for this
      * kind. Field diffusions run one step per kernel pass in passes of their own
      * (consecutive ones of distinct attributes share a pass) -- except a program that is
-     * exactly one field diffusion, on a one-attribute engine of a single slab without a
-     * halo (nranks == 1, MM_HALO_NONE): its passes fuse up to MM_FIELD_MAX_STEPS steps on
-     * mm_fieldk_kernel (MM_FIELD_STEPS; by default on slabs of 2^22 cells and more), bit for
-     * bit the same result. */
+     * exactly one field diffusion on a one-attribute engine: its passes fuse up to
+     * MM_FIELD_MAX_STEPS steps on mm_fieldk_kernel (MM_FIELD_STEPS; by default on slabs of
+     * 2^22 cells and more), bit for bit the same result. On a single slab without a halo
+     * (nranks == 1, MM_HALO_NONE) that is all; on a slab with a halo (a chain, any halo
+     * mode, MM_SELF_HALO) a K-step pass also reads K ghost rows of the rate field, which
+     * the engine never exchanges: K = min(that K, MM_FIELD_HALO, the chain's thinnest
+     * slab), so without MM_FIELD_HALO such slabs keep one step per pass. */
     MM_FLOW_DIFFUSE_FIELD = 3
 };
 
@@ -230,14 +233,19 @@ int mm_device_synchronize(int device);
  * polling),
  * MM_FIELD_STEPS (steps per pass of a program that is one rate-field diffusion: 1 one step
  * per pass, 2..MM_FIELD_MAX_STEPS that K on mm_fieldk_kernel, 0 or unset the default by
- * slab size; MM_PASSK=0 also means one step per pass there) and
+ * slab size; MM_PASSK=0 also means one step per pass there),
+ * MM_FIELD_HALO (d = 1..MM_FIELD_MAX_STEPS: the caller's promise that on every side where
+ * this slab has a neighbour every rate field gets d valid ghost rows, which lets the
+ * rate-field passes of a slab with a halo fuse up to d steps; unset, 0, 1 or anything else:
+ * 1, one step per pass there) and
  * MM_KERNEL_VARIANT (non-temporal stores;
  * the four-attribute K = 8 instances always store non-temporal) override tuning;
  * MM_SELF_HALO=1 with MM_HALO_RCCL and nranks == 1 makes the rank
  * exchange border rows with itself (ghost rows outside the grid: exercises the RCCL
  * path, result unchanged).
  * An RCCL chain runs in lockstep: every rank must call mm_prepare / mm_run with the same
- * step counts and reduce_every, with the same MM_GRAPH* settings and the same timing mode
+ * step counts and reduce_every, with the same MM_GRAPH* settings, the same MM_FIELD_HALO
+ * (like every plan input it is rank-invariant) and the same timing mode
  * (mm_set_timing), so that all ranks run the same K-row exchanges and capture the same
  * graphs at the same call (the first capture of each graph agrees on success with one
  * all-reduce, after draining this engine's streams). */
@@ -271,12 +279,18 @@ int mm_add_flow(mm_engine* eng, int kind, int a, int b, double rate);
  * allocating it drops the cached graphs). mm_rate_field_upload copies nrows rows of W
  * doubles starting at LOCAL row row0 (as mm_debug_read_rows: -kGhost <= row0, row0 + nrows
  * <= h + kGhost); rows outside the global grid are skipped, rows never uploaded are 0. In
- * a chain the caller supplies at least one ghost row on each side that has a neighbour:
- * the field is static, so the engine never exchanges it (MM_HALO_HOST and MM_HALO_RCCL
- * alike). Non-finite values, a bad range or a bad attr return MM_ERR_INVALID.
+ * a chain the caller supplies at least one ghost row on each side that has a neighbour --
+ * MM_FIELD_HALO ghost rows where the engine was created with that variable set: the field
+ * is static, so the engine never exchanges it (MM_HALO_HOST and MM_HALO_RCCL alike).
+ * Non-finite values, a bad range or a bad attr return MM_ERR_INVALID.
  * mm_rate_field_fill sets every in-grid row, ghost rows included, to value on the device.
  * Both are synchronous, like mm_upload, and do not reset steps_done. mm_run / mm_prepare of
- * a program with a field diffusion whose attribute has no field return MM_ERR_STATE. */
+ * a program with a field diffusion whose attribute has no field return MM_ERR_STATE. So do
+ * they, leaving no trace, when the program runs K-step field passes on a slab with a halo
+ * and, on a side with a neighbour, fewer than mm_info.halo_depth ghost rows of the field
+ * have been written since its allocation (counted contiguously outward from the slab; a
+ * fill counts for all, rows outside the grid count as written). That record only refuses:
+ * no plan depends on it. */
 int mm_rate_field_upload(mm_engine* eng, int attr, long long row0, long long nrows,
                          const double* host);
 int mm_rate_field_fill(mm_engine* eng, int attr, double value);

@@ -98,6 +98,11 @@ struct mm_engine {
     // attribute that has one, allocated and zeroed on first use; fld points at owned row 0
     double* fld_base[mm::kMaxAttr] = {};
     double* fld[mm::kMaxAttr] = {};
+    // ghost rows of each field written since its allocation, counted contiguously outward
+    // from the slab: [a][0] rows -1, -2, ..., [a][1] rows h, h+1, ... A record for check_run's
+    // refusal only -- it never feeds the plan (a plan depends on mm_desc, the creation
+    // environment and the flow list alone)
+    long long fld_rows[mm::kMaxAttr][2] = {};
     hipStream_t s_comp = nullptr, s_comm = nullptr;
     hipEvent_t ev_ready = nullptr, ev_halo = nullptr;
     hipEvent_t ev_comp_mark = nullptr, ev_comm_done = nullptr;
@@ -325,6 +330,9 @@ int slots_per_cu(mm_engine* e, mm::Kernel kernel, int k, bool red) {
     return s;
 }
 
+// The slab has a halo: a neighbour, or a halo mode on one slab (the self-halo among them).
+bool field_halo(const mm_engine* e) { return e->d.nranks > 1 || e->d.halo_mode != MM_HALO_NONE; }
+
 void sync_program(mm_engine* e) {  // the program's shape, for the planner
     mm::PlanIn& pin = e->pin;
     pin.n_passes = (int)e->passes.size();
@@ -341,13 +349,13 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     for (const Pass& q : e->passes)
         eight = eight || !q.pre.empty() || !q.post.empty() || q.field_mask != 0;
     pin.knobs.th = eight ? 8 : e->th_env;
-    // K-step rate-field passes (mm_fieldk_kernel): one attribute, one slab without a halo
-    // (so no self-halo either), and a program that is exactly one field diffusion. Chains
-    // would need K ghost rows of the field and border blocks, further attributes a copy.
-    const bool alone = e->na == 1 && e->d.nranks == 1 && e->d.halo_mode == MM_HALO_NONE &&
-                       !pin.split && p && p->field_mask == 1 && p->diffuse_mask == 0 &&
-                       !pin.chains;
-    pin.field_k = alone ? mm::field_steps_for(pin) : 0;
+    // K-step rate-field passes (mm_fieldk_kernel): one attribute and a program that is
+    // exactly one field diffusion (further attributes would need a copy). With a halo -- a
+    // chain, a self-halo, any halo mode -- K is also bounded by the ghost rows of the field
+    // the caller promised at creation (MM_FIELD_HALO, 1 unless set: one step per pass) and by
+    // the chain's thinnest slab; whether the rows are there is check_run's business.
+    const bool alone = e->na == 1 && p && p->field_mask == 1 && p->diffuse_mask == 0 && !pin.chains;
+    pin.field_k = alone ? mm::field_k_for(pin, field_halo(e)) : 0;
 }
 
 // Border-row exchange with both neighbours in one RCCL group: the first / last `depth`
@@ -1002,13 +1010,21 @@ int mm_rate_field_upload(mm_engine* e, int attr, long long row0, long long nrows
     // rows outside the global grid are skipped
     const long long lo = std::max(row0, -e->d.x_init);
     const long long hi = std::min(row0 + nrows, e->d.H - e->d.x_init);
-    if (hi <= lo) return MM_OK;
-    // the running steps read the field: on the compute stream (every run ends there), or on
-    // the comm stream behind an event the compute stream waits for
-    MM_HIP(hipMemcpy2DAsync(e->fld[attr] + lo * e->pitch, sizeof(double) * e->pitch,
-                            host + (lo - row0) * W, sizeof(double) * W, sizeof(double) * W,
-                            (size_t)(hi - lo), hipMemcpyHostToDevice, e->s_comp));
-    MM_HIP(hipStreamSynchronize(e->s_comp));
+    if (hi > lo) {
+        // the running steps read the field: on the compute stream (every run ends there), or
+        // on the comm stream behind an event the compute stream waits for
+        MM_HIP(hipMemcpy2DAsync(e->fld[attr] + lo * e->pitch, sizeof(double) * e->pitch,
+                                host + (lo - row0) * W, sizeof(double) * W, sizeof(double) * W,
+                                (size_t)(hi - lo), hipMemcpyHostToDevice, e->s_comp));
+        MM_HIP(hipStreamSynchronize(e->s_comp));
+    }
+    // the ghost rows this call wrote (or skipped as outside the grid), where they continue
+    // the rows already there: rows [row0, end) reach past row -1 - top / h + bottom
+    long long& top = e->fld_rows[attr][0];
+    long long& bottom = e->fld_rows[attr][1];
+    const long long end = row0 + nrows;
+    if (row0 < -top && end >= -top) top = -row0;
+    if (end > e->d.h + bottom && row0 <= e->d.h + bottom) bottom = end - e->d.h;
     return MM_OK;
 }
 
@@ -1020,6 +1036,7 @@ int mm_rate_field_fill(mm_engine* e, int attr, double value) {
     MM_HIP(mm::launch_fill(e->fld[attr], e->pitch, e->d.H, e->d.W, e->d.x_init, e->d.h,
                            MM_FILL_UNIFORM, value, 0, e->s_comp));
     MM_HIP(hipStreamSynchronize(e->s_comp));
+    e->fld_rows[attr][0] = e->fld_rows[attr][1] = mm::kGhost;  // every ghost row inside the grid
     return MM_OK;
 }
 
@@ -1059,6 +1076,27 @@ int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char
             if (((p.field_mask >> a) & 1) && !e->fld[a])
                 return fail(MM_ERR_STATE, std::string(who) + ": a rate-field diffusion's attribute has "
                                           "no field (mm_rate_field_upload / mm_rate_field_fill)");
+    // K-step rate-field passes with a halo read `depth` ghost rows of the field on every
+    // side that has a real neighbour (a self-halo side has none: its ghost rows lie outside
+    // the grid). The engine never exchanges the field: the caller promised the rows at
+    // creation (MM_FIELD_HALO), and a run without them is refused before it leaves a trace.
+    if (e->pin.field_k >= 2 && field_halo(e)) {
+        const long long depth = mm::steps_per_launch(e->pin);
+        const long long want[2] = {e->d.rank > 0 ? std::min<long long>(depth, e->d.x_init) : 0,
+                                   e->d.rank < e->d.nranks - 1
+                                       ? std::min<long long>(depth, e->d.H - e->d.x_init - e->d.h)
+                                       : 0};
+        for (int side = 0; side < 2; ++side)
+            if (e->fld_rows[0][side] < want[side]) {
+                char msg[256];
+                std::snprintf(msg, sizeof msg,
+                              "%s: K-step rate-field passes read %lld ghost rows of the field of "
+                              "attribute 0 %s the slab (MM_FIELD_HALO), %lld have been uploaded "
+                              "(mm_rate_field_upload / mm_rate_field_fill)",
+                              who, want[side], side == 0 ? "above" : "below", e->fld_rows[0][side]);
+                return fail(MM_ERR_STATE, msg);
+            }
+    }
     if (e->d.halo_mode == MM_HALO_HOST && e->d.nranks > 1) {
         if (e->passes.size() != 1)
             return fail(MM_ERR_STATE, std::string(who) + ": the host halo transport runs one-pass flow programs only");
@@ -1114,9 +1152,16 @@ int mm_prepare(mm_engine* e, long long nsteps, long long reduce_every) {
     // dispatch started 172 us after its launch, profiles/r06/hiptrace). No step runs: no
     // buffer is read or written.
     if (mm::kstep_ok(e->pin) && tail > 0) {
-        const int red = reduce_every > 0;  // the instance primed
-        for (int k : mm::pass_lengths(e->pin, tail))
+        // the instances primed: each pass's own, with the step sums where one of its steps
+        // is reduced and without where none is (a run may use both), the interior's on the
+        // compute stream and a split pass's border instance on the comm stream
+        long long s = phase + (nsteps - tail) + 1;
+        for (int k : mm::pass_lengths(e->pin, tail)) {
+            int red = 0;
+            for (int j = 0; j < k; ++j) red |= reduce_every > 0 && (s + j) % reduce_every == 0;
             MM_TRY(enqueue_pass(e, e->passes[0], k, red, false, true));
+            s += k;
+        }
         MM_HIP(hipStreamSynchronize(e->s_comp));
         if (e->pin.split) MM_HIP(hipStreamSynchronize(e->s_comm));
     }

@@ -1,8 +1,10 @@
 // mm_fieldk.hpp -- K fused steps of the rate-field diffusion (MM_FLOW_DIFFUSE_FIELD) per
 // HBM pass, gfx950: temporal blocking of mm_field_kernel's step for a program that is one
-// field diffusion of one attribute on a slab without a halo. A pass reads every cell's value
-// and rate once, advances the value K steps in registers and writes it once: 24/K B per
-// cell-update instead of 24 B.
+// field diffusion of one attribute. A pass reads every cell's value and rate once, advances
+// the value K steps in registers and writes it once: 24/K B per cell-update instead of 24 B.
+// On a slab with a halo the interior rows run the segment schedule beside the exchange and
+// the K border rows of each side the BLOCK schedule after it (fieldk_block below), which
+// reads K ghost rows of the state and of the rate field (MM_FIELD_HALO, include/mpimodel.h).
 //
 // The schedule is mm_passk_kernel's SEGMENT schedule (mm_passk.hpp, header comment), whose
 // strips, lane layout, wave map and descriptors it shares: a wave loads 128 columns (lane
@@ -261,11 +263,78 @@ __device__ __forceinline__ void fieldk_segment(const PassArgs& A, const Lane& c,
     if (RED) write_sums<K, 1>(A, wid, lane, acc);
 }
 
-// K steps of a one-attribute rate-field diffusion per launch, segment schedule (A.th /
-// A.th_edge rows per wave, mm_passk.hpp seg_map). RED: per-level sums of the owned cells
-// into partials[(partial_base + wave) * K + level]. NT & 1: non-temporal stores. Two waves
-// per SIMD at least: 256 registers per lane.
-template <int K, bool RED, int NT>
+// BLOCK schedule (mm_passk.hpp passk_block): TH output rows, the border rows of a halo-split
+// pass. Every one of the TH + 3K - 1 iterations is unrolled at compile time: level fill
+// states, row offsets and block ownership are constants, and so is the rate row of every
+// level -- the TH + 2K rate rows are loaded once and stay in registers (4 VGPRs per row and
+// lane), no ring, no reload. Level j's m-th input is row (j-1) + m of the block's input rows
+// rA-K .. rA+TH+K-1. A block cut short by the range's end (rB < rA + TH) reads zeros past
+// its descriptors; the rows past rB are neither stored nor summed.
+template <int K, int TH, bool RED, bool FAST>
+__device__ __forceinline__ void fieldk_block(const PassArgs& A, const Lane& c, long long wid,
+                                             int lane, int rA, int rB, unsigned voff,
+                                             unsigned soff) {
+    constexpr int NI = TH + 2 * K;       // input rows
+    constexpr int NIT = TH + 3 * K - 1;  // iterations
+    constexpr int U = 4;                 // state rows prefetched
+    double acc[K][1];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j][0] = 0.0;
+    const unsigned rowb = (unsigned)(A.pitch * 8);
+    const FBufs<K> B(A, rA, rB);
+    dv2 rawv[U], rawf[NI];
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        if (k < U) rawv[k] = load_row(B.in, voff + k * rowb);
+        rawf[k] = load_row(B.fld, voff + k * rowb);
+    }
+    FWin win[K];
+    double pend0[K], pend1[K];  // level j's row of the previous iteration: pend[j-1]
+
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+#pragma unroll
+        for (int j = K; j >= 1; --j) {  // descending: pend[j-2] is read before it is refilled
+            const int m = i - 3 * (j - 1);
+            if (m < 0 || m >= NI - 2 * (j - 1)) continue;  // compile-time
+            double v0, v1;
+            if (j == 1) {
+                v0 = rawv[i % U].x;
+                v1 = rawv[i % U].y;
+                if (i + U < NI) rawv[i % U] = load_row(B.in, voff + (i + U) * rowb);
+            } else {
+                v0 = pend0[j - 2];
+                v1 = pend1[j - 2];
+            }
+            const int row = (j - 1) + m;  // of the block's input rows: the level's rate row
+            const long long gx = c.gx0 + rA - K + row;
+            if (m < 2) {
+                fk_fill<FAST>(c, gx, m, win[j - 1], v0, v1, rawf[row].x, rawf[row].y);
+                continue;
+            }
+            double w0, w1;
+            fk_emit<FAST>(c, gx, win[j - 1], v0, v1, rawf[row].x, rawf[row].y, w0, w1);
+            const int orow = m + j - K - 2;  // output row - rA (compile-time)
+            if (RED && orow >= 0 && orow < TH) accum(acc[j - 1][0], rA + orow < rB, c, w0, w1);
+            if (j == K) {
+                store_row<0>(B.out, soff + orow * rowb, w0, w1);
+            } else {
+                pend0[j - 1] = w0;
+                pend1[j - 1] = w1;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // keep the row order: bounds the live registers
+    }
+    if (RED) write_sums<K, 1>(A, wid, lane, acc);
+}
+
+// K steps of a one-attribute rate-field diffusion per launch. MODE: kSeg = segment schedule
+// (A.th / A.th_edge rows per wave, mm_passk.hpp seg_map), else the block schedule with MODE
+// rows per wave (the border rows of a halo-split pass). The wave map is mm_passk_kernel's:
+// waves below A.waves_a work in rows [ra0, ra1), the others in [rb0, rb1). RED: per-level
+// sums of the owned cells into partials[(partial_base + wave) * K + level]. NT & 1:
+// non-temporal stores (segment schedule). Two waves per SIMD at least: 256 registers per lane.
+template <int K, int MODE, bool RED, int NT>
 __global__ __launch_bounds__(kBlock, 2) void mm_fieldk_kernel(const PassArgs A) {
     static_assert(K >= 2 && K <= kFieldMaxSteps, "mm_geom.hpp: kFieldMaxSteps");
     constexpr int L = (K + 1) / 2;          // halo lanes per side
@@ -275,8 +344,24 @@ __global__ __launch_bounds__(kBlock, 2) void mm_fieldk_kernel(const PassArgs A) 
     const long long wid = (long long)blockIdx.x * kWavesPerBlock + wave;
     if (wid >= A.waves_total) return;
 
+    int rlo, rhi;
+    long long w = wid;
+    if (w < A.waves_a) {
+        rlo = A.ra0;
+        rhi = A.ra1;
+    } else {
+        w -= A.waves_a;
+        rlo = A.rb0;
+        rhi = A.rb1;
+    }
     int strip, rA, rB;
-    seg_map(wid, A.ra0, A.ra1, A.nstrips, A.th, A.th_edge, strip, rA, rB);
+    if (MODE == kSeg) {
+        seg_map(w, rlo, rhi, A.nstrips, A.th, A.th_edge, strip, rA, rB);
+    } else {
+        strip = (int)(w % A.nstrips);
+        rA = rlo + (int)(w / A.nstrips) * MODE;
+        rB = min(rA + MODE, rhi);
+    }
 
     const long long W = A.W;
     const long long c0 = (long long)strip * OC - 2 * L;  // first loaded column (even)
@@ -299,22 +384,33 @@ __global__ __launch_bounds__(kBlock, 2) void mm_fieldk_kernel(const PassArgs A) 
     // a wave whose input rows and loaded columns are all interior (cnt == 8 everywhere)
     // runs the branch-free body; edge waves run the general one
     const bool fast = c.fast_cols && c.gx0 + rA - K >= 1 && c.gx0 + rB + K - 1 <= A.H - 2;
-    if (fast)
-        fieldk_segment<K, RED, NT, true>(A, c, wid, lane, rA, rB, voff, soff);
-    else
-        fieldk_segment<K, RED, NT, false>(A, c, wid, lane, rA, rB, voff, soff);
+    if constexpr (MODE == kSeg) {
+        if (fast)
+            fieldk_segment<K, RED, NT, true>(A, c, wid, lane, rA, rB, voff, soff);
+        else
+            fieldk_segment<K, RED, NT, false>(A, c, wid, lane, rA, rB, voff, soff);
+    } else {
+        if (fast)
+            fieldk_block<K, MODE, RED, true>(A, c, wid, lane, rA, rB, voff, soff);
+        else
+            fieldk_block<K, MODE, RED, false>(A, c, wid, lane, rA, rB, voff, soff);
+    }
 }
 
-// The instances of one K: with or without non-temporal stores, with the step sums or
+// The instances of one K: the segment schedule with or without non-temporal stores, the
+// border blocks of kBorderRows rows (q.nt does not apply), each with the step sums or
 // without. nullptr for another kernel's key.
 template <int K>
 const KernelInst* fieldk_inst(const InstKey& q) {
-    if (q.family != kInstFieldK || q.k != K || q.na != 1 || q.cols != 2 || !q.seg) return nullptr;
+    if (q.family != kInstFieldK || q.k != K || q.na != 1 || q.cols != 2) return nullptr;
+    if (!q.seg)
+        return q.red ? inst_of<mm_fieldk_kernel<K, kBorderRows, true, 0>, kBlock>()
+                     : inst_of<mm_fieldk_kernel<K, kBorderRows, false, 0>, kBlock>();
     if (q.nt)
-        return q.red ? inst_of<mm_fieldk_kernel<K, true, 1>, kBlock>()
-                     : inst_of<mm_fieldk_kernel<K, false, 1>, kBlock>();
-    return q.red ? inst_of<mm_fieldk_kernel<K, true, 0>, kBlock>()
-                 : inst_of<mm_fieldk_kernel<K, false, 0>, kBlock>();
+        return q.red ? inst_of<mm_fieldk_kernel<K, kSeg, true, 1>, kBlock>()
+                     : inst_of<mm_fieldk_kernel<K, kSeg, false, 1>, kBlock>();
+    return q.red ? inst_of<mm_fieldk_kernel<K, kSeg, true, 0>, kBlock>()
+                 : inst_of<mm_fieldk_kernel<K, kSeg, false, 0>, kBlock>();
 }
 
 }  // namespace

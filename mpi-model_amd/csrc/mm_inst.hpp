@@ -110,9 +110,9 @@ const KernelInst* find_inst(const InstKey& q);
 // segment, segment schedule only (a.seg; a.th / a.th_edge rows per block, a.waves_a /
 // a.waves_total count BLOCKS), a.nstrips = ceil(W / wide_out_cols(k, c)); sums into
 // partials[block][k][na].
-// mm_fieldk_kernel (one attribute, one rate-field diffusion, K 2..kFieldMaxSteps): segment
-// schedule only (a.seg), one row range (a.ra0, a.ra1), a.field[0] the rate field; strips,
-// waves and partials as mm_passk_kernel's.
+// mm_fieldk_kernel (one attribute, one rate-field diffusion, K 2..kFieldMaxSteps): a.seg:
+// segment schedule; else 4-row border blocks (a.th = kBorderRows); a.field[0] the rate field;
+// strips, row ranges, waves and partials as mm_passk_kernel's.
 // hipErrorInvalidValue for a key no unit builds.
 hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s);
 

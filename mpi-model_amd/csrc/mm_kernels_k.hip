@@ -94,6 +94,7 @@ hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s) {
     long long blocks = std::max<long long>(a.waves_total, 1);  // mm_wide_kernel: one per segment
     if (q.family == kInstFieldK) {
         if (!a.field[0] || a.field_mask != 1) return hipErrorInvalidValue;
+        if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
         blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
     } else if (q.family == kInstPassK) {
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;

@@ -48,6 +48,7 @@ const KnobRow kKnobRows[] = {
     {"MM_SELF_HALO", 'i', -kAny, kAny, [](Knobs& k, double v) { k.self_halo = v != 0; }},
     {"MM_KERNEL_VARIANT", 'i', 0, kAny, [](Knobs& k, double v) { k.variant = (int)std::min(v, 1e9); }},
     {"MM_FIELD_STEPS", 'i', 0, kFieldMaxSteps, [](Knobs& k, double v) { k.field_steps = (int)v; }},
+    {"MM_FIELD_HALO", 'i', 1, kFieldMaxSteps, [](Knobs& k, double v) { k.field_halo = (int)v; }},
 };
 
 }  // namespace
@@ -227,6 +228,11 @@ bool fieldk_on(const PlanIn& in) { return in.field_k >= 2; }
 constexpr int kFieldAutoSteps = 4;
 constexpr double kFieldAutoCells = 4194304.0;  // 2048^2
 static_assert(kFieldAutoCells >= 65536.0 && kFieldAutoSteps <= kFieldMaxSteps, "auto rule");
+// The same rule on a slab with a halo (field_k_for), by the cells of the chain's thinnest
+// slab: the smallest measured slab at which the split K = 4 pass beat the split one-step pass
+// of the same run (the table of tools/bench_field.py --self-halo).
+constexpr double kFieldAutoCellsHalo = 4194304.0;
+static_assert(kFieldAutoCellsHalo >= kFieldAutoCells, "a halo never lowers the auto threshold");
 
 }  // namespace
 
@@ -236,6 +242,17 @@ int field_steps_for(const PlanIn& in) {
         return 0;
     if (k >= 2) return std::min(k, kFieldMaxSteps);
     return (double)in.h * (double)in.W >= kFieldAutoCells ? kFieldAutoSteps : 0;
+}
+
+int field_k_for(const PlanIn& in, bool halo) {
+    if (!halo) return field_steps_for(in);
+    // sized by the chain's thinnest slab, like every plan input of a chain
+    PlanIn thin = in;
+    thin.h = in.min_rows;
+    int k = field_steps_for(thin);
+    if (in.knobs.field_steps == 0 && slab_cells(in) < kFieldAutoCellsHalo) k = 0;
+    k = (int)std::min<long long>(std::min(k, in.knobs.field_halo), in.min_rows);
+    return k >= 2 ? k : 0;
 }
 
 bool kstep_ok(const PlanIn& in) { return fieldk_on(in) || passk_ok(in); }
@@ -382,7 +399,6 @@ PassLaunches pass_launches(const PlanIn& in, int k, bool red) {
     const long long h = in.h;
     const int ns = kernel == kOneStep ? (int)(in.pitch / kStripCols) : (int)p.kern.strips;
     p.depth = kernel == kOneStep ? 1 : k;
-    // (a kFieldK pass is never split: field_k is set on slabs without a halo only)
     p.split = in.split && h >= 2 * p.depth + 1;  // else: slab too thin, one launch after the exchange
     auto blocks = [&](long long lo, long long hi, long long lo2, long long hi2, int th) {
         Launch l;
@@ -479,7 +495,8 @@ long long partials_need(const PlanIn& in) {
     // wave (+ 1-row border blocks); mm_passk_kernel, segments of >= 8 rows (edge strips)
     // plus 4-row border blocks (depth <= kGhost rows on each side) with K x NA sums per
     // wave: K <= kMaxSteps for one attribute, K <= 2 for up to kMaxAttr; mm_fieldk_kernel,
-    // segments of >= 16 rows over no more strips than these, K <= kFieldMaxSteps sums per wave
+    // segments of >= 8 rows over no more strips than these plus, split, one 4-row border
+    // block per strip and side, K <= kFieldMaxSteps sums per wave
     const long long ns1 = in.pitch / kStripCols;
     const long long need = (waves_for(ns1, in.h, 8) + 2 * waves_for(ns1, 2, 1) + 16) * kMaxAttr;
     const long long ns = ceil_div(in.W, passk_out_cols(kMaxSteps));

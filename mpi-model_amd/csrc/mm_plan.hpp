@@ -38,6 +38,9 @@ struct Knobs {
     int variant = -1;        // kernel tuning variant (MM_KERNEL_VARIANT; -1: by buffer size)
     int field_steps = 0;     // steps per rate-field pass (MM_FIELD_STEPS: 1 one step per pass,
                              // 2..kFieldMaxSteps that K on mm_fieldk_kernel; 0: auto)
+    int field_halo = 1;      // valid ghost rows of every rate field on each side that has a
+                             // neighbour, the caller's promise (MM_FIELD_HALO, 1..kFieldMaxSteps):
+                             // bounds the K of a rate-field pass on a slab with a halo
 };
 // `get` is std::getenv or a stand-in for it.
 Knobs read_knobs(const std::function<const char*(const char*)>& get);
@@ -57,9 +60,9 @@ struct PlanIn {
     bool chains = false;     // pre- or post-chain transfers
     bool ring = false;       // the ring instance runs its K = 8 passes (waves per workgroup)
     bool field = false;      // some pass is a rate-field pass (mm_field_kernel): one step per pass
-    int field_k = 0;         // >= 2: the program is one rate-field diffusion of one attribute on
-                             // a slab without a halo, and its passes fuse up to this many steps
-                             // on mm_fieldk_kernel (the engine sets field_steps_for; 0: off)
+    int field_k = 0;         // >= 2: the program is one rate-field diffusion of one attribute,
+                             // and its passes fuse up to this many steps on mm_fieldk_kernel
+                             // (the engine sets field_k_for; 0: off)
     Knobs knobs;
     int ncu = 0;             // compute units of the device
     // resident wave (kPassK, kFieldK) or workgroup (kWide) slots per CU of the instance that runs a
@@ -99,10 +102,15 @@ struct PassLaunches {
 // diffusion; several: diffusions and transfer chains), no rate-field pass, and buffer offsets
 // below 2^31.
 bool passk_ok(const PlanIn& in);
-// Steps per pass of a program that may run on mm_fieldk_kernel (one attribute, one slab, no
-// halo, exactly one rate-field diffusion -- the engine checks that): MM_FIELD_STEPS, or the
+// Steps per pass of a program that may run on mm_fieldk_kernel (one attribute, exactly one
+// rate-field diffusion -- the engine checks that) on a slab of in.h rows: MM_FIELD_STEPS, or the
 // auto rule by the slab's cells; 0 where it stays one step per pass (also with MM_PASSK=0).
 int field_steps_for(const PlanIn& in);
+// PlanIn::field_k of such a program. Without a halo: field_steps_for. With one (a chain, or
+// one slab with a halo mode): min(field_steps_for of the chain's thinnest slab,
+// MM_FIELD_HALO, min_rows) -- a K-step pass reads K ghost rows of the rate field, which the
+// engine never exchanges and the caller promises; under 2: 0.
+int field_k_for(const PlanIn& in, bool halo);
 // A run advances in K-step passes of the program's only pass: passk_ok, or field_k >= 2.
 bool kstep_ok(const PlanIn& in);
 KernelChoice kernel_for(const PlanIn& in, int k);

@@ -326,7 +326,8 @@ class Engine:
     def rate_field_upload(self, host, attr=0, row0=0):
         """Rows row0.. (local; ghost rows -20..-1 and h..h+19 included) of attr's rate field
         from a 2-D array of W columns. Rows never uploaded are 0; a slab of a chain uploads
-        its rows -1..h (clipped to the grid), the engine never exchanges the field."""
+        its rows -1..h (clipped to the grid; rows -d..h+d-1 where the engines were created
+        with MM_FIELD_HALO=d), the engine never exchanges the field."""
         a = np.ascontiguousarray(host, dtype=np.float64)
         assert a.ndim == 2 and a.shape[1] == self.W
         check(lib().mm_rate_field_upload(self.ptr, attr, row0, a.shape[0], _dptr(a)))

@@ -8,7 +8,19 @@ a launch, as a fraction of the 8 TB/s HBM peak; the arms alternate `--rounds` ti
 Needs a GPU; nothing here falls back.
 
   python tools/bench_field.py [--sizes 2048,4096,8192,16384] [--warmup 20] [--steps 200]
-                              [--rounds 3]
+                              [--rounds 3] [--self-halo]
+
+A size is N (an N x N grid) or HxW. Every arm also reports wall_step_us: host time per step
+of an untimed run of the same length (graph replay where the engine captures), the measure
+that includes a split pass's border launches and exchange, which the HIP events around the
+interior launch do not.
+
+--self-halo creates the engines with MM_HALO_RCCL, MM_SELF_HALO=1 and MM_FIELD_HALO=4: one
+rank that exchanges its border rows with itself, the only way to run the split schedule
+(interior segments beside the exchange, border blocks after it) with RCCL on one GPU. The
+field arms alone run; the summary compares wall_step_us, and the last line derives the auto
+rule of a slab with a halo: the smallest shape at which split K = 4 beat the split one-step
+arm of the same run in every round.
 
 Every arm times at least --steps steps, rounded up to a multiple of its K. Prints one JSON
 line per arm and round, then per size a summary line. For the K arms the summary holds the
@@ -23,6 +35,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "mpi-model_amd"))
@@ -37,15 +50,21 @@ def out_cols(k):
     return 128 - 4 * ((k + 1) // 2)
 
 
-def engine(H, W, k):
+def engine(H, W, k, self_halo=False):
     """k = 0: the uniform one-step arm; 1: the one-step field pass; >= 2: the K-step pass."""
     env = {"MM_PASSK": "0"} if k == 0 else {"MM_FIELD_STEPS": str(k)}
-    old = {name: os.environ.get(name) for name in ("MM_PASSK", "MM_FIELD_STEPS")}
+    if self_halo:
+        env.update(MM_SELF_HALO="1", MM_FIELD_HALO=str(mm.FIELD_MAX_STEPS))
+    old = {name: os.environ.get(name)
+           for name in ("MM_PASSK", "MM_FIELD_STEPS", "MM_SELF_HALO", "MM_FIELD_HALO")}
     for name in old:
         os.environ.pop(name, None)
     os.environ.update(env)
     try:
-        e = mm.Engine(H, W)
+        if self_halo:
+            e = mm.Engine(H, W, halo_mode=mm.MM_HALO_RCCL, comm_id_bytes=mm.comm_id())
+        else:
+            e = mm.Engine(H, W)
     finally:
         for name, v in old.items():
             os.environ.pop(name, None)
@@ -77,7 +96,16 @@ def measure(e, cells, k, warmup, steps):
     assert n == steps // k, (n, steps, k)
     us = ms / n * 1e3
     bps = nbytes / (us * 1e-6)
+    # the same run untimed, by the host's clock: every launch of a split pass and its exchange
+    e.prepare(steps)
+    e.run(warmup)
+    e.synchronize()
+    t0 = time.perf_counter()
+    e.run(steps)
+    e.synchronize()
+    wall = (time.perf_counter() - t0) / steps * 1e6
     return {"steps": steps, "pass_us": round(us, 2), "step_us": round(us / k, 2),
+            "wall_step_us": round(wall, 2),
             "GCUPS": round(cells * k / us / 1e3, 1),
             "bytes_per_cell_update": round(nbytes / cells / k, 2), "TBps": round(bps / 1e12, 3),
             "of_peak": round(bps / PEAK, 3)}
@@ -88,8 +116,41 @@ def span(rows, key):
     return {"min": min(v), "max": max(v), "mean": round(sum(v) / len(v), 3)}
 
 
+def shape_of(size):
+    h, _, w = str(size).partition("x")
+    return int(h), int(w or h)
+
+
+def run_self_halo(size, a):
+    """The field arms on one self-halo rank: split passes, compared by wall_step_us."""
+    H, W = shape_of(size)
+    arms = {"field": 1, **{"field%d" % k: k for k in KS}}
+    engines = {name: engine(H, W, k, True) for name, k in arms.items()}
+    res = {name: [] for name in arms}
+    for rnd in range(a.rounds):
+        for name, e in engines.items():
+            r = measure(e, H * W, arms[name], a.warmup, a.steps)
+            res[name].append(r)
+            print(json.dumps({"arm": name, "self_halo": True, "round": rnd, "H": H, "W": W, **r}),
+                  flush=True)
+    for e in engines.values():
+        e.close()
+    out = {"summary": "rate-field passes, self-halo (split)", "H": H, "W": W, "rounds": a.rounds,
+           "arms": {}}
+    for name, rows in res.items():
+        out["arms"][name] = {key: span(rows, key) for key in ("pass_us", "step_us", "wall_step_us")}
+    for k in KS:
+        arm = out["arms"]["field%d" % k]
+        arm["speedup"] = round(out["arms"]["field"]["wall_step_us"]["mean"] /
+                               arm["wall_step_us"]["mean"], 3)
+        arm["beats_one_step"] = all(r["wall_step_us"] < f["wall_step_us"]
+                                    for r, f in zip(res["field%d" % k], res["field"]))
+    print(json.dumps(out), flush=True)
+    return out
+
+
 def run_size(size, a):
-    H = W = size
+    H, W = shape_of(size)
     arms = {"field": 1, **{"field%d" % k: k for k in KS}, "uniform": 0}
     engines = {name: engine(H, W, k) for name, k in arms.items()}
     res = {name: [] for name in arms}
@@ -108,7 +169,8 @@ def run_size(size, a):
            "target_met": min(ratios) >= 0.9, "arms": {}}
     for name, rows in res.items():
         out["arms"][name] = {key: span(rows, key) for key in
-                             ("pass_us", "step_us", "GCUPS", "bytes_per_cell_update", "TBps", "of_peak")}
+                             ("pass_us", "step_us", "wall_step_us", "GCUPS",
+                              "bytes_per_cell_update", "TBps", "of_peak")}
     bps1 = out["arms"]["field"]["TBps"]["mean"] * 1e12
     for k in KS:
         arm = out["arms"]["field%d" % k]
@@ -128,19 +190,32 @@ def run_size(size, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048,4096,8192,16384")
-    ap.add_argument("--size", type=int, default=0, help="one size (instead of --sizes)")
+    ap.add_argument("--size", default="", help="one size (instead of --sizes)")
+    ap.add_argument("--self-halo", action="store_true",
+                    help="MM_HALO_RCCL + MM_SELF_HALO=1 + MM_FIELD_HALO=4: the split schedule")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
-    sizes = [a.size] if a.size else [int(s) for s in a.sizes.split(",")]
+    sizes = [a.size] if a.size else a.sizes.split(",")
+    cells = lambda s: shape_of(s)[0] * shape_of(s)[1]  # noqa: E731
+    if a.self_halo:
+        table = {size: run_self_halo(size, a) for size in sizes}
+        kmax = "field%d" % KS[-1]
+        wins = [s for s in sorted(table, key=cells) if table[s]["arms"][kmax]["beats_one_step"]]
+        lost = [s for s in sorted(table, key=cells) if s not in wins]
+        print(json.dumps({"auto_rule": "MM_FIELD_STEPS unset, slab with a halo", "K": KS[-1],
+                          "threshold_cells": max(cells(wins[0]), 1 << 16) if wins else None,
+                          "shapes_won": wins, "shapes_lost": lost}), flush=True)
+        return
     table = {size: run_size(size, a) for size in sizes}
 
-    ref = 8192 if 8192 in table else max(table)
+    ref = "8192" if "8192" in table else max(table, key=cells)
     best = min(KS, key=lambda k: table[ref]["arms"]["field%d" % k]["step_us"]["mean"])
-    wins = [s for s in sorted(table) if table[s]["arms"]["field%d" % best]["beats_one_step"]]
+    wins = [s for s in sorted(table, key=cells)
+            if table[s]["arms"]["field%d" % best]["beats_one_step"]]
     print(json.dumps({"auto_rule": "MM_FIELD_STEPS unset", "reference_size": ref, "K": best,
-                      "threshold_cells": max(wins[0] * wins[0], 1 << 16) if wins else None,
+                      "threshold_cells": max(cells(wins[0]), 1 << 16) if wins else None,
                       "sizes_won": wins}), flush=True)
 
 
