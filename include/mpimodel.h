@@ -237,7 +237,12 @@ int mm_device_synchronize(int device);
  * MM_FIELD_HALO (d = 1..MM_FIELD_MAX_STEPS: the caller's promise that on every side where
  * this slab has a neighbour every rate field gets d valid ghost rows, which lets the
  * rate-field passes of a slab with a halo fuse up to d steps; unset, 0, 1 or anything else:
- * 1, one step per pass there) and
+ * 1, one step per pass there),
+ * MM_WIDE_COLS (6: every K = 20 pass whose shape allows it -- one attribute, no halo, no step
+ * sums in the pass, at least 577 columns -- runs as the fused pass of mm_wide6_kernel, the
+ * grid's frame at 4 columns per lane and its interior at 6, whatever the slab's size; 4:
+ * never; unset or anything else: on slabs of 2^27 cells and more; bit for bit the same
+ * result; mm_pass_kernel reports 6 columns per lane for such a pass) and
  * MM_KERNEL_VARIANT (non-temporal stores;
  * the four-attribute K = 8 instances always store non-temporal) override tuning;
  * MM_SELF_HALO=1 with MM_HALO_RCCL and nranks == 1 makes the rank

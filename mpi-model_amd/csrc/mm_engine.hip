@@ -319,11 +319,13 @@ int relabel(const mm_engine* e, mm::PassArgs& A) {
 
 // Resident slots per CU of the instance that runs a k-step pass (mm::PlanIn::slots): waves
 // of mm_passk_kernel, workgroups of mm_wide_kernel, from the instance's registers and LDS,
-// cached by instance. An unknown instance counts one slot, as a failed query does.
-int slots_per_cu(mm_engine* e, mm::Kernel kernel, int k, bool red) {
+// cached by instance. An unknown instance counts one slot, as a failed query does. cols: the
+// wide kernel's columns per lane where not its usual ones (mm_wide6_kernel: mm::kWide6Cols).
+int slots_per_cu(mm_engine* e, mm::Kernel kernel, int k, bool red, int cols = 0) {
     const bool wide = kernel == mm::kWide;
-    const mm::KernelInst* inst = mm::find_inst(
-        inst_key(e, kernel, k, wide ? (e->na > 1 ? 2 : 4) : 2, true, red, e->variant & 1));
+    if (!cols) cols = wide ? (e->na > 1 ? 2 : 4) : 2;
+    const mm::KernelInst* inst =
+        mm::find_inst(inst_key(e, kernel, k, cols, true, red, e->variant & 1));
     if (!inst) return 1;
     int& s = e->slots[inst];
     if (!s) s = std::max(1, mm::inst_blocks_per_cu(*inst) * (wide ? 1 : mm::kWavesPerBlock));
@@ -454,6 +456,10 @@ void set_launch(mm::PassArgs& A, const mm::Launch& l) {
     A.seg = l.seg, A.th = l.th, A.th_edge = l.th_edge, A.xcd_remap = l.xcd_remap;
     A.nstrips = l.nstrips;
     A.waves_a = l.waves_a, A.waves_total = l.waves_total, A.partial_base = l.partial_base;
+    const mm::Wide6& w = l.c6;  // the fused six-column pass (all 0 otherwise)
+    A.c6_top = w.top, A.c6_bot = w.bot, A.c6_col = w.col, A.c6_rcol = w.rcol;
+    A.c6_strips = w.strips, A.c6_rstrips = w.rstrips, A.c6_th = w.th;
+    A.c6_band0 = w.band0, A.c6_band1 = w.band1, A.c6_frame = w.frame;
 }
 
 // One kernel pass over the slab, as mm::pass_launches describes it: k fused steps of the
@@ -761,6 +767,7 @@ int mm_engine_create(const mm_desc* desc, mm_engine** out) {
     pin.knobs = mm::read_knobs([](const char* name) -> const char* { return std::getenv(name); });
     e->th_env = pin.knobs.th;
     pin.slots = [e](mm::Kernel kernel, int k, bool red) { return slots_per_cu(e, kernel, k, red); };
+    pin.slots6 = [e](int k) { return slots_per_cu(e, mm::kWide, k, false, mm::kWide6Cols); };
     e->variant = mm::kernel_variant(pin);
 
     auto cleanup = [&](int rc) {

@@ -20,6 +20,7 @@ constexpr int kBorderRows = 4;     // rows per wave of the K-step kernel's borde
 constexpr int kSegPrefetch1 = 8;   // mm_passk.hpp seg_prefetch<1>() (MM_SEG_U1)
 constexpr int kWide20Waves = 4;    // waves per workgroup, K = 20 (mm_wide_k20.hip: 20 / MM_K20_KW)
 constexpr int kWideRingWaves = 4;  // the ring instance (mm_widear_k8.hip: 8 / MM_WIDEAR_KW)
+constexpr int kWide6Cols = 6;      // columns per lane of mm_wide6_kernel's interior strips (K = 20)
 
 // 1 + (i > 0) + (i < n-1) inside [0, n), 0 outside: cnt = span(x)*span(y) - 1 (constexpr:
 // the kernels and the engine's host code share it)
@@ -62,6 +63,24 @@ inline bool wide_has(int k, int c, int na) {
 
 inline int wide_out_cols(int k, int c) {
     return 64 * c - 2 * c * ((k + c - 1) / c);  // 64 lanes less ceil(K / C) halo lanes a side
+}
+
+// Column tiling of the fused six-column K = 20 pass (mm_wide6_kernel): the frame's first strip
+// [0, col) at 4 columns per lane, `strips` strips of wide_out_cols(20, 6) columns from col on at
+// 6 columns per lane, and rstrips strips at 4 columns per lane over [rcol, W). The six-column
+// strips run the FAST body alone, so every column they load (one halo, 24 columns, past their
+// output columns) is an interior column of the grid: the right part keeps at least 25 columns,
+// the grid's last column among them. strips == 0: W too narrow.
+struct Wide6Cols {
+    int col, rcol, strips, rstrips;
+};
+inline Wide6Cols wide6_cols(long long W) {
+    const int o4 = wide_out_cols(kMaxWide, 4), o6 = wide_out_cols(kMaxWide, kWide6Cols);
+    const int halo = kWide6Cols * ((kMaxWide + kWide6Cols - 1) / kWide6Cols);
+    const long long room = W - o4 - (halo + 1);
+    const int n = room >= o6 && W < (1LL << 30) ? (int)(room / o6) : 0;
+    const int rcol = o4 + n * o6;
+    return {o4, rcol, n, n ? (int)((W - rcol + o4 - 1) / o4) : 0};
 }
 
 inline int wide_waves_per_block(int k, int c, int na, bool ring) {

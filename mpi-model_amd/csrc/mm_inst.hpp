@@ -88,6 +88,11 @@ MM_INST_DECL(wide_inst_k4) MM_INST_DECL(wide_inst_k8) MM_INST_DECL(wide_inst_k12
 MM_INST_DECL(wide_inst_k16) MM_INST_DECL(wide_inst_k20)
 MM_INST_DECL(wide_inst_k20_r0_n0) MM_INST_DECL(wide_inst_k20_r0_n1)
 MM_INST_DECL(wide_inst_k20_r1_n0) MM_INST_DECL(wide_inst_k20_r1_n1)
+MM_INST_DECL(wide_inst_k16_r0_n0) MM_INST_DECL(wide_inst_k16_r0_n1)  // K = 16: the same
+MM_INST_DECL(wide_inst_k16_r1_n0) MM_INST_DECL(wide_inst_k16_r1_n1)
+// mm_wide6_k20.hip: the fused K = 20 pass, cols = kWide6Cols (mm_wide6_kernel; one instance:
+// non-temporal stores, no sums)
+MM_INST_DECL(wide6_inst_k20)
 // four attributes, 2 columns per lane. mm_widea_k4.hip: any pass of K = 4;
 // mm_widear_k8.hip: the ring instance; mm_widea_k8.hip, one object per instance: nd = N
 // diffusing attributes with (P = 1) or without (P = 0) a post-chain

@@ -39,6 +39,14 @@ struct PassArgs {
     const double* field[kMaxAttr];  // mm_field_kernel: rate field of attribute a (row 0, same
                                     // pitch and ghost rows as the attribute buffers)
     int field_mask;         // bit a: attribute a diffuses by field[a] in this pass
+    // mm_wide6_kernel (mm_plan.hpp Wide6): rows [ra0, ra1), nstrips strips of the whole width
+    int c6_top, c6_bot;     // interior rows [c6_top, c6_bot) between the two row bands
+    int c6_col, c6_rcol;    // first output column of the six-column strips / of the strips
+                            // right of them
+    int c6_strips, c6_rstrips;  // six-column strips, strips right of them
+    int c6_th;              // rows per interior segment (th: per frame segment between the bands)
+    long long c6_band0, c6_band1, c6_frame;  // blocks before the end of the top band, of the
+                                             // bottom band, of the frame (then the interior's)
 };
 
 // Launchers (mm_kernels.hip). All enqueue on `s` and return the launch status.

@@ -74,7 +74,8 @@ const KernelInst* find_inst(const InstKey& q) {
         passk_inst_k1,     passk_inst_k2,     passk_inst_k3,     passk_inst_k4,
         passk_inst_k5,     passk_inst_k6,     passk_inst_k7,     passk_inst_k8,
         passk_inst_k9,     passk_inst_k10,    wide_inst_k4,      wide_inst_k8,
-        wide_inst_k12,     wide_inst_k16,     wide_inst_k20,     widea_inst_k4,
+        wide_inst_k12,     wide_inst_k16,     wide_inst_k20,     wide6_inst_k20,
+        widea_inst_k4,
         widear_inst_k8,    widea8_inst_n1_p0, widea8_inst_n1_p1, widea8_inst_n2_p0,
         widea8_inst_n2_p1, widea8_inst_n3_p0, widea8_inst_n3_p1, widea8_inst_n4_p0,
         widea8_inst_n4_p1, fieldk_inst_k2,    fieldk_inst_k3,    fieldk_inst_k4};

@@ -49,6 +49,7 @@ const KnobRow kKnobRows[] = {
     {"MM_KERNEL_VARIANT", 'i', 0, kAny, [](Knobs& k, double v) { k.variant = (int)std::min(v, 1e9); }},
     {"MM_FIELD_STEPS", 'i', 0, kFieldMaxSteps, [](Knobs& k, double v) { k.field_steps = (int)v; }},
     {"MM_FIELD_HALO", 'i', 1, kFieldMaxSteps, [](Knobs& k, double v) { k.field_halo = (int)v; }},
+    {"MM_WIDE_COLS", 'i', 4, kWide6Cols, [](Knobs& k, double v) { if (v != 5) k.wide_cols = (int)v; }},
 };
 
 }  // namespace
@@ -264,12 +265,35 @@ bool passk_ok(const PlanIn& in) {
     return true;
 }
 
-KernelChoice kernel_for(const PlanIn& in, int k) {
+bool wide6_on(const PlanIn& in, int k, bool red) {
+    // planned from the fused instance's occupancy: a caller that has no such instance
+    // (slots6 unset) plans every pass at 4 columns
+    if (!in.slots6 || in.knobs.wide_cols == 4 || k != kMaxWide || red || in.n_attr != 1 || in.split ||
+        in.nranks != 1 || in.x_init != 0 || in.h != in.H || !use_wide(in, k))
+        return false;
+    if (wide6_cols(in.W).strips == 0) return false;
+    return in.knobs.wide_cols == kWide6Cols || slab_cells(in) >= kWideSplitCells;
+}
+
+namespace {
+
+// kernel_for but for the fused six-column pass
+KernelChoice kernel4_for(const PlanIn& in, int k) {
     // a rate-field program in K-step passes: a pass of one step stays on mm_field_kernel
     if (fieldk_on(in) && k >= 2) return {kFieldK, 2, ceil_div(in.W, passk_out_cols(k))};
     if (!passk_ok(in)) return {kOneStep, 1, 0};  // one mm_pass_kernel launch per pass of the step
     if (use_wide(in, k)) return {kWide, wcols(in), ceil_div(in.W, wide_out_cols(k, wcols(in)))};
     return {kPassK, 2, ceil_div(in.W, passk_out_cols(k))};
+}
+
+}  // namespace
+
+KernelChoice kernel_for(const PlanIn& in, int k, bool red) {
+    if (wide6_on(in, k, red)) {  // the strips between the bands: first, six-column, right
+        const Wide6Cols c = wide6_cols(in.W);
+        return {kWide, kWide6Cols, 1 + c.strips + c.rstrips};
+    }
+    return kernel4_for(in, k);
 }
 
 int steps_per_launch(const PlanIn& in) {
@@ -388,13 +412,60 @@ Segments segments(const PlanIn& in, Kernel kernel, int k, int slots, long long n
 }
 
 Segments segments(const PlanIn& in, int k, bool red, long long lo, long long hi) {
-    const KernelChoice kc = kernel_for(in, k);
+    const KernelChoice kc = kernel4_for(in, k);  // (the six-column pass: wide6_launch)
     return segments(in, kc.kernel, k, std::max(1, in.slots(kc.kernel, k, red)), hi - lo, kc.strips);
 }
 
+namespace {
+
+int slots6_of(const PlanIn& in, int k) { return std::max(1, in.slots6(k)); }
+
+// The fused six-column pass of the whole grid (wide6_on). Columns: wide6_cols. Rows: the
+// interior strips run the FAST body from their first pipeline iteration to their last, so
+// every row a level of them reads -- rows top - k .. bot + k - 1 -- lies in [2, H - 3]; top and
+// bot even (the interior segments then all start at even rows: no odd-start shift). A grid too
+// low for interior rows is all band. One segment length for the frame's strips between the
+// bands and the six-column strips: segments() of all of them at the fused instance's occupancy.
+Launch wide6_launch(const PlanIn& in, int k) {
+    const Wide6Cols c = wide6_cols(in.W);
+    const long long h = in.h;
+    Launch l;
+    l.lo = 0, l.hi = h, l.seg = 1;
+    l.nstrips = (int)ceil_div(in.W, wide_out_cols(k, 4));
+    Wide6& w = l.c6;
+    w.col = c.col, w.rcol = c.rcol, w.strips = c.strips, w.rstrips = c.rstrips;
+    w.top = (int)std::min<long long>(k + 2, h);
+    w.bot = (int)std::max<long long>(w.top, (h - k - 2) & ~1LL);
+    w.band0 = l.nstrips;
+    w.band1 = w.band0 + (w.bot < h ? l.nstrips : 0);
+    w.frame = w.band1;
+    l.waves_total = w.band1;
+    const long long n = w.bot - w.top;
+    if (n > 0) {
+        const long long ns = 1 + c.rstrips + c.strips;
+        const Segments s = segments(in, kWide, k, slots6_of(in, k), n, ns);
+        l.th = l.th_edge = w.th = s.th;
+        const long long per = ceil_div(n, s.th);
+        w.frame = w.band1 + (1 + c.rstrips) * per;
+        l.waves_total = w.frame + c.strips * per;
+    } else {
+        l.th = l.th_edge = w.th = 2;  // (no block between the bands)
+    }
+    l.waves_a = l.waves_total;
+    return l;
+}
+
+}  // namespace
+
 PassLaunches pass_launches(const PlanIn& in, int k, bool red) {
     PassLaunches p{};
-    p.kern = kernel_for(in, k);
+    p.kern = kernel_for(in, k, red);
+    if (p.kern.cols == kWide6Cols && p.kern.kernel == kWide) {
+        p.depth = k;
+        p.interior = wide6_launch(in, k);
+        p.total = p.interior.waves_total;
+        return p;
+    }
     const Kernel kernel = p.kern.kernel;
     const long long h = in.h;
     const int ns = kernel == kOneStep ? (int)(in.pitch / kStripCols) : (int)p.kern.strips;
@@ -444,8 +515,12 @@ SlabPlan slab_plan(const PlanIn& in) {
     const KernelChoice kc = kernel_for(in, spl);
     if (kc.kernel == kOneStep)
         return {kOneStep, spl, in.knobs.th, waves_for(in.pitch / kStripCols, in.h, in.knobs.th), 0};
+    if (kc.cols == kWide6Cols && kc.kernel == kWide) {  // the fused six-column pass's own plan
+        const Launch l = wide6_launch(in, spl);
+        return {kWide, spl, l.th, l.waves_total * kWide20Waves, slots6_of(in, spl) * kWide20Waves};
+    }
     const Segments s = segments(in, spl, false, 0, in.h);
-    const int per = kc.kernel == kWide ? wide_waves_per_block(spl, kc.cols, in.n_attr, in.ring) : 1;
+    const int per =kc.kernel == kWide ? wide_waves_per_block(spl, kc.cols, in.n_attr, in.ring) : 1;
     return {kc.kernel, spl, s.th, s.count * per, std::max(1, in.slots(kc.kernel, spl, false)) * per};
 }
 

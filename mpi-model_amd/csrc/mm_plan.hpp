@@ -41,6 +41,8 @@ struct Knobs {
     int field_halo = 1;      // valid ghost rows of every rate field on each side that has a
                              // neighbour, the caller's promise (MM_FIELD_HALO, 1..kFieldMaxSteps):
                              // bounds the K of a rate-field pass on a slab with a halo
+    int wide_cols = 0;       // MM_WIDE_COLS: 6 the fused six-column K = 20 pass wherever its
+                             // shape allows (wide6_on), 4 never; 0 auto: slabs of >= 2^27 cells
 };
 // `get` is std::getenv or a stand-in for it.
 Knobs read_knobs(const std::function<const char*(const char*)>& get);
@@ -68,6 +70,9 @@ struct PlanIn {
     // resident wave (kPassK, kFieldK) or workgroup (kWide) slots per CU of the instance that runs a
     // pass of k steps, with the step sums or without: the one plan input the device gives
     std::function<int(Kernel, int k, bool red)> slots;
+    // workgroup slots per CU of the fused six-column instance of k steps (mm_wide6_kernel);
+    // unset: the caller has no such instance, and every pass plans at 4 columns
+    std::function<int(int k)> slots6;
 };
 
 struct KernelChoice {
@@ -81,11 +86,26 @@ struct Segments {
     long long count;   // waves (kPassK, kFieldK) or workgroups (kWide)
 };
 
+// The fused six-column pass (mm_wide.hpp mm_wide6_kernel), one launch of rows [lo, hi) = the
+// whole grid. Frame, at 4 columns per lane, dispatched first: the band rows [lo, top) and
+// [bot, hi) of every column (Launch::nstrips strips), and between the bands the strip of the
+// grid's first column and the rstrips strips from column rcol on (the grid's last column
+// among them, whatever W % 6 is) in segments of Launch::th rows. Interior: `strips` strips of
+// wide_out_cols(k, 6) columns from column col on at 6 columns per lane, rows [top, bot) in
+// segments of th rows; every row and column any level of them reads is an interior cell.
+// Blocks [0, band0) the top band, [band0, band1) the bottom band, [band1, frame) the frame
+// between the bands, [frame, Launch::waves_total) the interior. strips == 0: not such a pass.
+struct Wide6 {
+    int top = 0, bot = 0, col = 0, rcol = 0, strips = 0, rstrips = 0, th = 0;
+    long long band0 = 0, band1 = 0, frame = 0;
+};
+
 // One kernel launch: rows [lo, hi) and [lo2, hi2) of the slab, as mm::PassArgs wants them.
 struct Launch {
     long long lo = 0, hi = 0, lo2 = 0, hi2 = 0;
     int seg = 0, th = 0, th_edge = 0, xcd_remap = 0, nstrips = 0;
     long long waves_a = 0, waves_total = 0, partial_base = 0;
+    Wide6 c6;
 };
 
 // One pass: the interior launch on the compute stream and, when split, the border launch
@@ -113,7 +133,13 @@ int field_steps_for(const PlanIn& in);
 int field_k_for(const PlanIn& in, bool halo);
 // A run advances in K-step passes of the program's only pass: passk_ok, or field_k >= 2.
 bool kstep_ok(const PlanIn& in);
-KernelChoice kernel_for(const PlanIn& in, int k);
+// red: the pass sums some of its steps (only the choice of the six-column pass depends on it)
+KernelChoice kernel_for(const PlanIn& in, int k, bool red = false);
+// The fused six-column pass runs a k-step pass: MM_WIDE_COLS not 4, one attribute on the wide
+// kernel, k = 20, an unsplit pass of the whole grid (no halo), no sums, W wide enough for one
+// six-column strip between the frame's parts (wide6_cols) and, unless MM_WIDE_COLS=6, a slab
+// of >= 2^27 cells.
+bool wide6_on(const PlanIn& in, int k, bool red);
 // Steps one kernel pass advances: K with the K-step kernels, 1 otherwise. Also the ghost
 // rows one exchange must fill.
 int steps_per_launch(const PlanIn& in);

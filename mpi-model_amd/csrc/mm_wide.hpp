@@ -28,6 +28,10 @@
 // diffusions) hold NA windows per level: C = 2 columns per lane keeps the state of a level
 // near a one-attribute level's at C = 4 (NA * C doubles per cell row).
 //
+// C = 6 columns per lane (halo ceil(20/6) = 4 lanes a side, 30 fp64 + 4 DPP per level-row)
+// holds in 256 registers only without the EDGE / GEN windows: mm_wide6_kernel below runs
+// the interior of large K = 20 slabs so, FAST-only, and the grid's frame at C = 4.
+//
 // C = 8 columns per lane, column waves, an LDS-DMA input ring, role rotation and
 // non-temporal loads were built, measured and dropped (git history).
 //
@@ -819,7 +823,7 @@ __device__ __forceinline__ void wave_dispatch(const WCtx<C, NA>& x, int iend,
 template <int C, int NA, int KW, int P, int U, int B, bool RED, int NT>
 __device__ __forceinline__ void wide_segment(const PassArgs& A, dv2* lds, int p, int lane,
                                              int strip, int rA, int rB,
-                                             double (&carry)[KW][NA]) {
+                                             double (&carry)[KW][NA], long long col0 = 0) {
     using G = WGeom<KW, P, B>;
     constexpr int K = G::K;
     constexpr int LH = (K + C - 1) / C;       // halo lanes per side
@@ -837,8 +841,9 @@ __device__ __forceinline__ void wide_segment(const PassArgs& A, dv2* lds, int p,
     x.rB = rB;
     const long long W = A.W;
     // first loaded column: the strip's span starts C * LH columns before its first output
-    // column
-    const long long c0 = (long long)strip * OC - C * LH;
+    // column; col0 (a multiple of C): the first output column of strip 0 (mm_wide6_kernel's
+    // strips right of the six-column ones)
+    const long long c0 = col0 + (long long)strip * OC - C * LH;
     const long long y0 = c0 + C * lane;
     const bool in_row = y0 >= 0 && y0 < A.pitch;  // y0 % C == 0, pitch % 128 == 0
     const bool store_lane = lane >= LH && lane < 64 - LH && y0 < W;
@@ -945,6 +950,113 @@ __global__ __launch_bounds__(64 * P, MW) void mm_wide_kernel(const PassArgs A) {
                 A.partials[((A.partial_base + blk) * K + p * KW + q) * NA + a] = carry[q][a];
         }
     }
+}
+
+// ---- FAST-only strips (mm_wide6_kernel's interior blocks) --------------------------------
+// A strip segment whose every loaded column and every row any level reads is an interior
+// cell of the grid (the planner's promise, mm_plan.cpp wide6_plan): the schedule of
+// wave_run with the FAST body alone -- the MID prologue and FAST groups up to iend, no wm
+// windows, no EDGE / GEN code, no sums. The iterations past the segment's last row (iend is
+// a whole number of groups) read rows past the descriptor (0) and their stores are dropped.
+template <int C, int KW, int P, int U, int B, int NT, int ROLE, int PP>
+__device__ __forceinline__ void wave_run_fast(const WCtx<C, 1>& x, int iend) {
+    static_assert(B % U == 0, "ring slots repeat within a group");
+    WState<C, 1, KW, U> st;
+    const int s = wave_prologue<C, 1, KW, P, U, B, false, NT, ROLE, kBodyFast, PP>(x, st);
+    wave_groups<C, 1, KW, P, U, B, false, NT, kBodyFast, ROLE, PP>(x, st, s, iend);
+}
+
+// Segment [rA, rB) of the FAST-only strip whose first output column is col (even, so the
+// lanes' first columns are even and wemit's column pairing holds), one attribute.
+template <int C, int KW, int P, int U, int B, int NT>
+__device__ __forceinline__ void fast_segment(const PassArgs& A, dv2* lds, int p, int lane,
+                                             long long col, int rA, int rB) {
+    using G = WGeom<KW, P, B>;
+    constexpr int K = G::K;
+    constexpr int LH = (K + C - 1) / C;  // halo lanes per side
+    constexpr int RW = 32 * C;           // dv2 per LDS row
+    WCtx<C, 1> x;
+    const int sh = (int)((A.x_init + rA - K) & 1);  // odd first input row: wide_segment
+    x.rA = rA - sh;
+    x.oA = rA;
+    x.rB = rB;
+    const long long y0 = col - C * LH + C * lane;  // >= 0: the strips lie right of the frame's
+    const bool in_row = y0 >= 0 && y0 + C <= A.pitch;
+    const bool store_lane = lane >= LH && lane < 64 - LH && y0 + C <= A.W;
+    x.rowb = (unsigned)(A.pitch * 8);
+    x.voff = (in_row ? (unsigned)(y0 * 8) : kOOB) - (unsigned)sh * x.rowb;
+    x.soff = store_lane ? (unsigned)(y0 * 8) : kOOB;
+    x.c.H = A.H;
+    x.p = p;
+    x.lane = lane;
+    x.start = p * G::D;
+    x.dmask = 1;
+    x.g0 = A.x_init + x.rA - K;
+    x.r8[0] = A.drate[0] * 0.125;
+    x.in[0] = rows_rsrc(A.in[0] + (long long)(rA - K) * A.pitch, rB - rA + 2 * K, A.pitch);
+    x.out[0] = rows_rsrc(A.out[0] + (long long)rA * A.pitch, rB - rA, A.pitch);
+    x.none = rows_rsrc(A.out[0], 0, A.pitch);
+    x.lds_in = p > 0 ? lds + (p - 1) * G::RL * RW : lds;
+    x.lds_out = p < P - 1 ? lds + p * G::RL * RW : lds;
+    x.A = &A;
+    const int need = (P - 1) * G::D + G::S0 + (x.rB - x.rA);
+    const int iend = (need + G::B - 1) / G::B * G::B;
+    constexpr bool kMidPar = ((KW | G::D) & 1) != 0;
+    if (p == 0)
+        wave_run_fast<C, KW, P, U, B, NT, kRoleFirst, 0>(x, iend);
+    else if (p == P - 1)
+        wave_run_fast<C, KW, P, U, B, NT, kRoleLast, (P - 1) & 1>(x, iend);
+    else if (kMidPar && (p & 1))
+        wave_run_fast<C, KW, P, U, B, NT, kRoleMid, 1>(x, iend);
+    else
+        wave_run_fast<C, KW, P, U, B, NT, kRoleMid, 0>(x, iend);
+}
+
+// One K = KW * P step pass of one attribute without sums, the columns between the grid's
+// edge strips at CI columns per lane: one launch whose workgroups take one of two paths by
+// block index (the plan: mm_plan.cpp wide6_plan; every part's blocks by seg_map with one
+// segment length).
+//   Frame blocks, dispatched first: wide_segment at CF columns per lane with the FAST, EDGE
+//   and GEN bodies, unchanged -- the band rows [0, A.c6_top) and [A.c6_bot, ra1) of every
+//   column (A.nstrips strips of the whole width), and between the bands strip 0 (the grid's
+//   first column) and the A.c6_rstrips strips from column A.c6_rcol on (the grid's last
+//   column, whatever W % CI is).
+//   Interior blocks: fast_segment at CI columns per lane on the A.c6_strips strips from
+//   column A.c6_col on, rows [A.c6_top, A.c6_bot) in segments of A.c6_th rows.
+template <int CF, int CI, int KW, int P, int MW, int U, int B, int NT>
+__global__ __launch_bounds__(64 * P, MW) void mm_wide6_kernel(const PassArgs A) {
+    using G = WGeom<KW, P, B>;
+    constexpr int K = G::K;
+    constexpr int LHI = (K + CI - 1) / CI;
+    constexpr int OCI = 64 * CI - 2 * CI * LHI;  // output columns of an interior strip
+    static_assert(CI >= CF && CI % 2 == 0 && OCI % 2 == 0, "the LDS rows hold either path's");
+    __shared__ dv2 lds[(P - 1) * G::RL * 32 * CI];
+    const int lane = threadIdx.x & 63;
+    const int p = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // level group
+    long long w = blockIdx.x;
+    if (w >= A.waves_total) return;  // the whole block: no barrier is left waiting
+    int strip, rA, rB;
+    if (w >= A.c6_frame) {
+        seg_map(w - A.c6_frame, A.c6_top, A.c6_bot, A.c6_strips, A.c6_th, A.c6_th, strip, rA, rB);
+        fast_segment<CI, KW, P, U, B, NT>(A, lds, p, lane, A.c6_col + (long long)strip * OCI, rA,
+                                          rB);
+        return;
+    }
+    double carry[KW][1];  // (no sums)
+    long long col0 = 0;
+    if (w < A.c6_band0) {  // the top band
+        seg_map(w, A.ra0, A.c6_top, A.nstrips, A.c6_top - A.ra0, A.c6_top - A.ra0, strip, rA, rB);
+    } else if (w < A.c6_band1) {  // the bottom band
+        seg_map(w - A.c6_band0, A.c6_bot, A.ra1, A.nstrips, A.ra1 - A.c6_bot, A.ra1 - A.c6_bot,
+                strip, rA, rB);
+    } else {  // between the bands: the first strip and the strips right of the interior's
+        seg_map(w - A.c6_band1, A.c6_top, A.c6_bot, 1 + A.c6_rstrips, A.th, A.th, strip, rA, rB);
+        if (strip > 0) {
+            col0 = A.c6_rcol;
+            strip -= 1;
+        }
+    }
+    wide_segment<CF, 1, KW, P, U, B, false, NT>(A, lds, p, lane, strip, rA, rB, carry, col0);
 }
 
 // Does the key select this shape of mm_wide_kernel? (Segment schedule only.)

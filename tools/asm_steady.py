@@ -5,7 +5,12 @@ mix (tools/asm_loops.py's counters) -- the evidence that the production loops is
 modelled 20 fp64 + 4 DPP per level-row on average (5 per cell: the box-sum step of round 6,
 22 on an even row and 18 on the odd row after it) and no scratch.
 
-usage: asm_steady.py FILE.s KERNEL_SUBSTRING DPP_PER_TRIP
+The model per level-row of a lane of C columns is 5 C fp64 + 4 DPP: 5 x DPP_PER_TRIP fp64 per
+trip at C = 4 (the default), 7.5 x at C = 6 -- mm_wide6_kernel's interior loops, 600 fp64 and
+80 DPP per 4 rows x 5 levels: `asm_steady.py FILE.s mm_wide6_kernel 80 6`. (The same kernel's
+frame loops are the C = 4 ones: `... 80`.)
+
+usage: asm_steady.py FILE.s KERNEL_SUBSTRING DPP_PER_TRIP [COLUMNS_PER_LANE]
 """
 import re
 import sys
@@ -16,6 +21,8 @@ from asm_loops import kernel_lines, mix  # noqa: E402
 
 def main():
     path, sub, dpp = sys.argv[1], sys.argv[2], int(sys.argv[3])
+    cols = int(sys.argv[4]) if len(sys.argv) > 4 else 4
+    f64 = 5 * cols * dpp // 4  # 5 C fp64 per 4 DPP
     body = kernel_lines(path, sub)
     labels = {}
     for i, l in enumerate(body):
@@ -31,7 +38,7 @@ def main():
         if tgt in labels and labels[tgt] < i:
             c = mix(body[labels[tgt]:i + 1])
             key = tuple(sorted(c.items()))
-            if c.get("dpp") == dpp and c.get("f64", 0) == 5 * dpp and key not in seen:
+            if c.get("dpp") == dpp and c.get("f64", 0) == f64 and key not in seen:
                 seen.add(key)
                 role = "first wave (loads)" if c.get("bload") else (
                     "last wave (stores)" if c.get("bstore") else "middle wave (LDS in/out)")

@@ -19,7 +19,7 @@ import re
 import statistics
 import sys
 
-KERNEL_RE = re.compile(r"mm_(pass[2k]?|wide)_kernel")
+KERNEL_RE = re.compile(r"mm_(pass[2k]?|wide6?)_kernel")
 SUM_RE = re.compile(r"mm_(finalize|level_sums|hist_advance)")
 
 
