@@ -67,8 +67,10 @@ enum mm_flow_kind {
      * every operation a separate IEEE fp64 one (no fused multiply-add, the IEEE division):
      * bit for bit or_field_step_general of oracle/mm_oracle.c with outf = f * v. A field
      * that is zero except at chosen cells is a multi-source flow, a constant field the
-     * whole-grid flow, a 0/1-scaled field a mask. mm_add_flow ignores b and rate for this
-     * kind. Field diffusions run one step per kernel pass in passes of their own
+     * whole-grid flow. A 0/1-scaled field masks EMISSION only: a cell of rate 0 emits
+     * nothing, yet its neighbours still count it and send it their shares (a sink); for a
+     * domain whose zero-rate cells are walls see MM_FLOW_DIFFUSE_CLOSED. mm_add_flow ignores
+     * b and rate for this kind. Field diffusions run one step per kernel pass in passes of their own
      * (consecutive ones of distinct attributes share a pass) -- except a program that is
      * exactly one field diffusion on a one-attribute engine: its passes fuse up to
      * MM_FIELD_MAX_STEPS steps on mm_fieldk_kernel (MM_FIELD_STEPS; by default on slabs of
@@ -77,7 +79,37 @@ enum mm_flow_kind {
      * mode, MM_SELF_HALO) a K-step pass also reads K ghost rows of the rate field, which
      * the engine never exchanges: K = min(that K, MM_FIELD_HALO, the chain's thinnest
      * slab), so without MM_FIELD_HALO such slabs keep one step per pass. */
-    MM_FLOW_DIFFUSE_FIELD = 3
+    MM_FLOW_DIFFUSE_FIELD = 3,
+    /* The rate-field diffusion on a closed, irregular domain: attribute a diffuses by its
+     * rate field f, and a cell of rate zero is a wall. A cell is OPEN when it is inside the
+     * grid and f(c) != 0.0 (+0 and -0 are both walls); everything else is a wall. For the
+     * in-grid cell c = (x, y):
+     *   cnt(c) = number of OPEN Moore neighbours of c                          (0..8)
+     *   out(c) = f(c) * v(c)              if c is open and cnt(c) > 0, else 0  (by select)
+     *   s(c)   = out(c) * 0.125           if cnt(c) == 8
+     *            out(c) / (double)cnt(c)  if 1 <= cnt(c) <= 7                  (IEEE division)
+     *            0                        otherwise: walls, cnt == 0, any cell outside the
+     *                                     grid                                 (by select)
+     *   q(x,y) = s(x-1,y) + s(x+1,y)
+     *   t(x,y) = q(x,y) + s(x,y)
+     *   nb     = (t(x,y-1) + t(x,y+1)) + q(x,y)
+     *   v'(c)  = (v(c) - out(c)) + nb     if c is open
+     *            v(c), bit for bit        if c is a wall
+     * every operation a separate IEEE fp64 one, in the order and association of
+     * MM_FLOW_DIFFUSE_FIELD: where f != 0 on the whole grid this IS that kind, bit for bit.
+     * A wall is a wall by select, never by multiplication: a wall holding NaN, an infinity
+     * or -0 keeps exactly those bits and changes no other cell, and the quantity is
+     * conserved over the open cells. mm_add_flow ignores b and rate for this kind. Each
+     * closed diffusion is a kernel pass of its own (mm_closed_kernel), and a program that
+     * holds one runs one step per pass, halo depth 1, whatever MM_FIELD_STEPS and
+     * MM_FIELD_HALO say (mm_info.kernel and mm_pass_kernel report 0). One step reads v of
+     * rows x-1..x+1 but f of rows x-2..x+2 (the share of row x+1 needs the count of row
+     * x+1, which needs the openness of row x+2). So on a slab with a halo (a chain, any halo
+     * mode, MM_SELF_HALO) the engine must have been created with MM_FIELD_HALO=2 or more,
+     * and two ghost rows of the field (rows -2..h+1, clipped to the grid) must have been
+     * uploaded on every side with a neighbour: mm_run / mm_prepare return MM_ERR_STATE
+     * otherwise, before anything is enqueued. */
+    MM_FLOW_DIFFUSE_CLOSED = 4
 };
 
 enum mm_fill_mode {

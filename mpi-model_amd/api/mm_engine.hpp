@@ -32,6 +32,8 @@ public:
     void add_flow(int kind, int a, int b, double rate) { check(mm_add_flow(e_, kind, a, b, rate)); }
     // diffusion of attr by its per-cell rate field (MM_FLOW_DIFFUSE_FIELD)
     void add_diffuse_field(int attr) { check(mm_add_flow(e_, MM_FLOW_DIFFUSE_FIELD, attr, attr, 0.0)); }
+    // the same on a closed domain: cells of rate zero are walls (MM_FLOW_DIFFUSE_CLOSED)
+    void add_diffuse_closed(int attr) { check(mm_add_flow(e_, MM_FLOW_DIFFUSE_CLOSED, attr, attr, 0.0)); }
     // nrows rows of W rates from local row row0 (ghost rows included) / one rate everywhere
     void rate_field_upload(int attr, long long row0, long long nrows, const double* host) {
         check(mm_rate_field_upload(e_, attr, row0, nrows, host));

@@ -6,7 +6,8 @@
 //   * a one-pass flow program runs K steps per kernel pass (mm_passk_kernel, temporal
 //     blocking: 16/K B of HBM traffic per cell-update); other programs run one step
 //     per pass (mm_pass_kernel; mm_field_kernel for a rate-field pass, whose per-cell rate
-//     map is one more static buffer of the same shape per attribute);
+//     map is one more static buffer of the same shape per attribute; mm_closed_kernel for a
+//     closed rate-field pass, in which cells of rate zero are walls);
 //   * a compute stream and a comm stream; with a halo (RCCL or host transport) each pass
 //     runs the interior rows on the compute stream while the `depth` border rows wait
 //     for the exchange on the comm stream (RCCL: ncclSend/ncclRecv of `depth` rows to
@@ -76,6 +77,9 @@ struct Pass {
     int diffuse_mask = 0;
     double drate[mm::kMaxAttr] = {0, 0, 0, 0};
     int field_mask = 0;
+    // a closed rate-field diffusion (MM_FLOW_DIFFUSE_CLOSED, mm_closed_kernel): the pass holds
+    // that one flow alone, field_mask its attribute's bit
+    bool closed = false;
 };
 
 struct FlowDesc {
@@ -166,6 +170,17 @@ int compile_passes(mm_engine* e) {
     Pass cur;
     bool open = false;
     for (const FlowDesc& f : e->flows) {
+        // a closed diffusion is a pass of its own: it closes any open pass and shares its
+        // own with nothing
+        if (f.kind == MM_FLOW_DIFFUSE_CLOSED) {
+            if (open) e->passes.push_back(cur);
+            open = false;
+            Pass c;
+            c.field_mask = 1 << f.a;
+            c.closed = true;
+            e->passes.push_back(c);
+            continue;
+        }
         // rate-field diffusions get passes of their own: consecutive ones of distinct
         // attributes share a pass; any other flow closes it, and they close any other pass
         const bool fieldf = f.kind == MM_FLOW_DIFFUSE_FIELD;
@@ -342,8 +357,11 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     pin.diffuse_mask = p ? p->diffuse_mask : 0;
     pin.chains = p && !(p->pre.empty() && p->post.empty());
     pin.ring = wring(e);
-    pin.field = false;
-    for (const Pass& q : e->passes) pin.field = pin.field || q.field_mask != 0;
+    pin.field = pin.closed = false;
+    for (const Pass& q : e->passes) {
+        pin.field = pin.field || q.field_mask != 0;
+        pin.closed = pin.closed || q.closed;  // one step per pass, whatever the knobs say
+    }
     // transfers, several attributes or a rate field: those kernels exist for 8-row blocks
     // only. Any other program, the empty one included, gets the height the environment asked
     // for back: a reprogrammed engine plans as a fresh one (include/mpimodel.h, mm_clear_flows)
@@ -356,7 +374,8 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     // chain, a self-halo, any halo mode -- K is also bounded by the ghost rows of the field
     // the caller promised at creation (MM_FIELD_HALO, 1 unless set: one step per pass) and by
     // the chain's thinnest slab; whether the rows are there is check_run's business.
-    const bool alone = e->na == 1 && p && p->field_mask == 1 && p->diffuse_mask == 0 && !pin.chains;
+    const bool alone = e->na == 1 && p && p->field_mask == 1 && !p->closed && p->diffuse_mask == 0 &&
+                       !pin.chains;
     pin.field_k = alone ? mm::field_k_for(pin, field_halo(e)) : 0;
 }
 
@@ -439,11 +458,13 @@ int unsplit_halo(mm_engine* e, int depth) {
 
 // One kernel launch of a pass on a stream. A border launch takes no tuning variant.
 int launch(mm_engine* e, const mm::PassLaunches& pl, bool red, const mm::PassArgs& A, hipStream_t s,
-           bool border) {
+           bool border, bool closed) {
     const int nt = border ? 0 : e->variant;
     if (pl.kern.kernel != mm::kOneStep)  // mm_passk_kernel, mm_wide_kernel, mm_fieldk_kernel
         MM_HIP(mm::launch_kstep(
             inst_key(e, pl.kern.kernel, pl.depth, pl.kern.cols, A.seg != 0, red, nt & 1), A, s));
+    else if (closed)  // a closed rate-field pass
+        MM_HIP(mm::launch_closed(e->na, red, A, s, nt));
     else if (A.field_mask)  // a rate-field pass
         MM_HIP(mm::launch_field(e->na, red, A, s, nt));
     else
@@ -485,8 +506,8 @@ int enqueue_pass(mm_engine* e, const Pass& p, int k, int mask, bool time_it, boo
     if (prime) {
         A.waves_total = B.waves_total = 0;
         A.waves_a = B.waves_a = -1;
-        MM_TRY(launch(e, pl, red, A, e->s_comp, false));
-        if (pl.split) MM_TRY(launch(e, pl, red, B, e->s_comm, true));
+        MM_TRY(launch(e, pl, red, A, e->s_comp, false, p.closed));
+        if (pl.split) MM_TRY(launch(e, pl, red, B, e->s_comm, true, p.closed));
         return MM_OK;
     }
     if (pl.split)
@@ -504,11 +525,11 @@ int enqueue_pass(mm_engine* e, const Pass& p, int k, int mask, bool time_it, boo
                              (double)(pl.interior.hi - pl.interior.lo) * (double)e->d.W;
         MM_HIP(hipEventRecord(t0, e->s_comp));
     }
-    MM_TRY(launch(e, pl, red, A, e->s_comp, false));
+    MM_TRY(launch(e, pl, red, A, e->s_comp, false, p.closed));
     if (time_it) MM_HIP(hipEventRecord(t1, e->s_comp));
     if (pl.split) {
         MM_TRY(split_comm(e, pl.depth));
-        MM_TRY(launch(e, pl, red, B, e->s_comm, true));
+        MM_TRY(launch(e, pl, red, B, e->s_comm, true, p.closed));
         MM_HIP(hipEventRecord(e->ev_comm_done, e->s_comm));
         e->comm_live = true;
         if (red) MM_HIP(hipStreamWaitEvent(e->s_comp, e->ev_comm_done, 0));
@@ -959,12 +980,14 @@ int mm_clear_flows(mm_engine* e) {
 
 int mm_add_flow(mm_engine* e, int kind, int a, int b, double rate) {
     if (!e) return fail(MM_ERR_INVALID, "mm_add_flow: null");
-    if (kind != MM_FLOW_DIFFUSE && kind != MM_FLOW_TRANSFER && kind != MM_FLOW_DIFFUSE_FIELD)
+    if (kind != MM_FLOW_DIFFUSE && kind != MM_FLOW_TRANSFER && kind != MM_FLOW_DIFFUSE_FIELD &&
+        kind != MM_FLOW_DIFFUSE_CLOSED)
         return fail(MM_ERR_INVALID, "mm_add_flow: unknown flow kind");
     if (a < 0 || a >= e->na) return fail(MM_ERR_INVALID, "mm_add_flow: attribute out of range");
     if (kind == MM_FLOW_TRANSFER && b >= e->na)
         return fail(MM_ERR_INVALID, "mm_add_flow: target attribute out of range");
-    if (kind == MM_FLOW_DIFFUSE_FIELD) rate = 0.0;  // the rate is the attribute's field
+    // the rate is the attribute's field
+    if (kind == MM_FLOW_DIFFUSE_FIELD || kind == MM_FLOW_DIFFUSE_CLOSED) rate = 0.0;
     if (!std::isfinite(rate)) return fail(MM_ERR_INVALID, "mm_add_flow: rate must be finite");
     MM_TRY(set_device(e));
     MM_HIP(hipStreamSynchronize(e->s_comp));
@@ -1101,6 +1124,32 @@ int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char
                               "attribute 0 %s the slab (MM_FIELD_HALO), %lld have been uploaded "
                               "(mm_rate_field_upload / mm_rate_field_fill)",
                               who, want[side], side == 0 ? "above" : "below", e->fld_rows[0][side]);
+                return fail(MM_ERR_STATE, msg);
+            }
+    }
+    // A closed pass counts open neighbours: the share of the neighbour's border row needs
+    // that row's count, which reads the field one row further out. On a slab with a halo the
+    // caller promises two ghost rows of the field at creation (MM_FIELD_HALO=2) and uploads
+    // them on every side with a real neighbour; the plan itself never depends on either.
+    for (const Pass& p : e->passes) {
+        if (!p.closed || !field_halo(e)) continue;
+        const int a = __builtin_ctz((unsigned)p.field_mask);
+        if (e->pin.knobs.field_halo < 2)
+            return fail(MM_ERR_STATE, std::string(who) + ": a closed diffusion on a slab with a halo "
+                                      "reads two ghost rows of the field: create the engine with "
+                                      "MM_FIELD_HALO=2 (or more) and upload rows -2..h+1");
+        const long long want[2] = {e->d.rank > 0 ? std::min<long long>(2, e->d.x_init) : 0,
+                                   e->d.rank < e->d.nranks - 1
+                                       ? std::min<long long>(2, e->d.H - e->d.x_init - e->d.h)
+                                       : 0};
+        for (int side = 0; side < 2; ++side)
+            if (e->fld_rows[a][side] < want[side]) {
+                char msg[256];
+                std::snprintf(msg, sizeof msg,
+                              "%s: a closed diffusion reads %lld ghost rows of the field of "
+                              "attribute %d %s the slab (MM_FIELD_HALO=2), %lld have been uploaded "
+                              "(mm_rate_field_upload / mm_rate_field_fill)",
+                              who, want[side], a, side == 0 ? "above" : "below", e->fld_rows[a][side]);
                 return fail(MM_ERR_STATE, msg);
             }
     }

@@ -1,5 +1,5 @@
 // mm_internal.hpp -- shared between the gfx950 kernels (mm_kernels.hip, mm_field.hip,
-// mm_kernels_k.hip) and the engine / C ABI (mm_engine.hip). The K-step kernels' instances
+// mm_closed.hip, mm_kernels_k.hip) and the engine / C ABI (mm_engine.hip). The K-step kernels' instances
 // and their launch: mm_inst.hpp. Not part of the public boundary.
 #pragma once
 
@@ -56,6 +56,10 @@ hipError_t launch_pass(int na, bool reduce, const PassArgs& a, hipStream_t s, in
 // ranges, wave mapping and partials as launch_pass; a.th 8, or 1 (border rows). variant bit
 // 0: non-temporal stores (one attribute).
 hipError_t launch_field(int na, bool reduce, const PassArgs& a, hipStream_t s, int variant);
+// One step of a closed rate-field pass (mm_closed_kernel, mm_closed.hip): the one attribute of
+// a.field_mask diffuses by a.field[] among the cells whose rate is not zero, walls keep their
+// bits, the other attributes are copied through. Arguments as launch_field.
+hipError_t launch_closed(int na, bool reduce, const PassArgs& a, hipStream_t s, int variant);
 // Append the levels of `mask` (bit j: step j of a K-step pass) of partials[n][k][na],
 // each summed in a fixed order, to the history (na sums per entry).
 // perm: partials slot i holds attribute (perm >> 2i) & 3 (relabelled passes).

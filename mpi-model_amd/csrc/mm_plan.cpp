@@ -220,7 +220,7 @@ double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
 
 long long waves_for(long long nstrips, long long n, int th) { return n <= 0 ? 0 : nstrips * ceil_div(n, th); }
 
-bool fieldk_on(const PlanIn& in) { return in.field_k >= 2; }
+bool fieldk_on(const PlanIn& in) { return in.field_k >= 2 && !in.closed; }
 
 // MM_FIELD_STEPS unset: K = kFieldAutoSteps on slabs of at least kFieldAutoCells cells
 // (the table of tools/bench_field.py: the built K of the best time per step
@@ -246,6 +246,7 @@ int field_steps_for(const PlanIn& in) {
 }
 
 int field_k_for(const PlanIn& in, bool halo) {
+    if (in.closed) return 0;  // mm_closed_kernel runs one step per pass
     if (!halo) return field_steps_for(in);
     // sized by the chain's thinnest slab, like every plan input of a chain
     PlanIn thin = in;

@@ -62,6 +62,9 @@ struct PlanIn {
     bool chains = false;     // pre- or post-chain transfers
     bool ring = false;       // the ring instance runs its K = 8 passes (waves per workgroup)
     bool field = false;      // some pass is a rate-field pass (mm_field_kernel): one step per pass
+    bool closed = false;     // some pass is a closed rate-field pass (mm_closed_kernel): field is
+                             // set too, and the program stays at one step per pass, halo depth
+                             // 1, whatever MM_FIELD_STEPS / MM_FIELD_HALO say (field_k_for: 0)
     int field_k = 0;         // >= 2: the program is one rate-field diffusion of one attribute,
                              // and its passes fuse up to this many steps on mm_fieldk_kernel
                              // (the engine sets field_k_for; 0: off)
@@ -129,7 +132,8 @@ int field_steps_for(const PlanIn& in);
 // PlanIn::field_k of such a program. Without a halo: field_steps_for. With one (a chain, or
 // one slab with a halo mode): min(field_steps_for of the chain's thinnest slab,
 // MM_FIELD_HALO, min_rows) -- a K-step pass reads K ghost rows of the rate field, which the
-// engine never exchanges and the caller promises; under 2: 0.
+// engine never exchanges and the caller promises; under 2: 0. A program with a closed
+// diffusion (in.closed): 0.
 int field_k_for(const PlanIn& in, bool halo);
 // A run advances in K-step passes of the program's only pass: passk_ok, or field_k >= 2.
 bool kstep_ok(const PlanIn& in);

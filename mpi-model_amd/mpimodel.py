@@ -18,6 +18,7 @@ MM_OK = 0
 MM_FLOW_DIFFUSE = 1
 MM_FLOW_TRANSFER = 2
 MM_FLOW_DIFFUSE_FIELD = 3
+MM_FLOW_DIFFUSE_CLOSED = 4
 FIELD_MAX_STEPS = 4  # MM_FIELD_MAX_STEPS: most steps mm_fieldk_kernel fuses per pass (MM_FIELD_STEPS)
 MM_FILL_UNIFORM = 0
 MM_FILL_RANDOM = 1
@@ -322,6 +323,12 @@ class Engine:
     def add_diffuse_field(self, attr):
         """Diffusion of `attr` by its per-cell rate field (rate_field_upload / rate_field_fill)."""
         check(lib().mm_add_flow(self.ptr, MM_FLOW_DIFFUSE_FIELD, attr, attr, 0.0))
+
+    def add_diffuse_closed(self, attr):
+        """Diffusion of `attr` by its rate field on a closed domain: cells of rate zero are
+        walls that take no share, give none and keep their bits (MM_FLOW_DIFFUSE_CLOSED). A
+        slab of a chain is created with MM_FIELD_HALO=2 and uploads field rows -2..h+1."""
+        check(lib().mm_add_flow(self.ptr, MM_FLOW_DIFFUSE_CLOSED, attr, attr, 0.0))
 
     def rate_field_upload(self, host, attr=0, row0=0):
         """Rows row0.. (local; ghost rows -20..-1 and h..h+19 included) of attr's rate field

@@ -8,7 +8,7 @@ a launch, as a fraction of the 8 TB/s HBM peak; the arms alternate `--rounds` ti
 Needs a GPU; nothing here falls back.
 
   python tools/bench_field.py [--sizes 2048,4096,8192,16384] [--warmup 20] [--steps 200]
-                              [--rounds 3] [--self-halo]
+                              [--rounds 3] [--self-halo] [--closed]
 
 A size is N (an N x N grid) or HxW. Every arm also reports wall_step_us: host time per step
 of an untimed run of the same length (graph replay where the engine captures), the measure
@@ -21,6 +21,14 @@ rank that exchanges its border rows with itself, the only way to run the split s
 field arms alone run; the summary compares wall_step_us, and the last line derives the auto
 rule of a slab with a halo: the smallest shape at which split K = 4 beat the split one-step
 arm of the same run in every round.
+
+--closed runs the closed rate-field pass (MM_FLOW_DIFFUSE_CLOSED, mm_closed_kernel) instead
+of the K arms: `field`, the one-step field pass as the baseline of the same run; `closed`, the
+same engine shape and the same mm_rate_field_fill(0.1) field, every cell open (the ballot
+takes the division-free body on every interior row); `closed_disc`, that field with a disc
+of walls of about a quarter of the grid in its middle (rows that cross the disc's rim run the
+general body, rows inside it the body of rows in which nothing emits). The summary's
+bytes_ratio is the all-open closed pass's bytes/s over the field pass's (target: >= 0.9).
 
 Every arm times at least --steps steps, rounded up to a multiple of its K. Prints one JSON
 line per arm and round, then per size a summary line. For the K arms the summary holds the
@@ -80,6 +88,57 @@ def engine(H, W, k, self_halo=False):
     want = (4, k) if k >= 2 else (0, 1)
     assert (info["kernel"], info["steps_per_launch"]) == want, info
     return e
+
+
+def closed_engine(H, W, disc):
+    """The closed pass on the field of the `field` arm; disc: a disc of walls of a quarter of
+    the grid's cells in the middle."""
+    old = {name: os.environ.pop(name, None) for name in ("MM_PASSK", "MM_FIELD_STEPS", "MM_SELF_HALO",
+                                                         "MM_FIELD_HALO")}
+    try:
+        e = mm.Engine(H, W)
+    finally:
+        os.environ.update({k: v for k, v in old.items() if v is not None})
+    e.fill_random(0)
+    e.rate_field_fill(0.1)
+    if disc:
+        import numpy as np
+        r2 = H * W / (4.0 * np.pi)
+        y = (np.arange(W) - (W - 1) / 2.0) ** 2
+        chunk = max(1, (1 << 24) // W)
+        for x0 in range(0, H, chunk):
+            x = (np.arange(x0, min(H, x0 + chunk)) - (H - 1) / 2.0) ** 2
+            e.rate_field_upload(np.where(x[:, None] + y[None, :] <= r2, 0.0, 0.1), row0=x0)
+    e.add_diffuse_closed(0)
+    info = e.info()
+    assert (info["kernel"], info["steps_per_launch"], info["n_passes"]) == (0, 1, 1), info
+    return e
+
+
+def run_closed(size, a):
+    """The closed pass, all open and around a disc of walls, beside the one-step field pass."""
+    H, W = shape_of(size)
+    engines = {"field": engine(H, W, 1), "closed": closed_engine(H, W, False),
+               "closed_disc": closed_engine(H, W, True)}
+    res = {name: [] for name in engines}
+    for rnd in range(a.rounds):
+        for name, e in engines.items():
+            r = measure(e, H * W, 1, a.warmup, a.steps)
+            res[name].append(r)
+            print(json.dumps({"arm": name, "round": rnd, "H": H, "W": W, **r}), flush=True)
+    for e in engines.values():
+        e.close()
+    ratios = [c["TBps"] / f["TBps"] for c, f in zip(res["closed"], res["field"])]
+    out = {"summary": "closed rate-field pass", "H": H, "W": W, "rounds": a.rounds,
+           "bytes_ratio": {"min": round(min(ratios), 3), "max": round(max(ratios), 3),
+                           "mean": round(sum(ratios) / len(ratios), 3)},
+           "target_met": min(ratios) >= 0.9, "arms": {}}
+    for name, rows in res.items():
+        out["arms"][name] = {key: span(rows, key) for key in
+                             ("pass_us", "wall_step_us", "GCUPS", "bytes_per_cell_update", "TBps",
+                              "of_peak")}
+    print(json.dumps(out), flush=True)
+    return out
 
 
 def measure(e, cells, k, warmup, steps):
@@ -193,12 +252,18 @@ def main():
     ap.add_argument("--size", default="", help="one size (instead of --sizes)")
     ap.add_argument("--self-halo", action="store_true",
                     help="MM_HALO_RCCL + MM_SELF_HALO=1 + MM_FIELD_HALO=4: the split schedule")
+    ap.add_argument("--closed", action="store_true",
+                    help="the closed pass (all open, and around a disc of walls) beside the field pass")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     sizes = [a.size] if a.size else a.sizes.split(",")
     cells = lambda s: shape_of(s)[0] * shape_of(s)[1]  # noqa: E731
+    if a.closed:
+        for size in sizes:
+            run_closed(size, a)
+        return
     if a.self_halo:
         table = {size: run_self_halo(size, a) for size in sizes}
         kmax = "field%d" % KS[-1]
