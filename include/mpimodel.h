@@ -32,6 +32,9 @@ extern "C" {
 /* Most steps one kernel pass of a rate-field diffusion fuses (mm_fieldk_kernel, K = 2 ..
  * MM_FIELD_MAX_STEPS; MM_FIELD_STEPS). */
 #define MM_FIELD_MAX_STEPS 4
+/* Most steps one kernel pass of a closed rate-field diffusion fuses (mm_closedk_kernel, K = 2
+ * .. MM_CLOSED_MAX_STEPS; MM_CLOSED_STEPS). */
+#define MM_CLOSED_MAX_STEPS 4
 
 enum mm_status {
     MM_OK = 0,
@@ -100,9 +103,14 @@ enum mm_flow_kind {
      * A wall is a wall by select, never by multiplication: a wall holding NaN, an infinity
      * or -0 keeps exactly those bits and changes no other cell, and the quantity is
      * conserved over the open cells. mm_add_flow ignores b and rate for this kind. Each
-     * closed diffusion is a kernel pass of its own (mm_closed_kernel), and a program that
-     * holds one runs one step per pass, halo depth 1, whatever MM_FIELD_STEPS and
-     * MM_FIELD_HALO say (mm_info.kernel and mm_pass_kernel report 0). One step reads v of
+     * closed diffusion is a kernel pass of its own (mm_closed_kernel), and MM_FIELD_STEPS
+     * and MM_FIELD_HALO have no effect on a program that holds one. Such a program runs one
+     * step per pass, halo depth 1 (mm_info.kernel and mm_pass_kernel report 0) -- except, with
+     * MM_CLOSED_STEPS=K (2..MM_CLOSED_MAX_STEPS) in the creation environment, a program that
+     * is exactly one closed diffusion on a one-attribute engine whose slab has no halo
+     * (nranks == 1, MM_HALO_NONE): its passes fuse up to K steps on mm_closedk_kernel
+     * (mm_info.kernel 5), bit for bit the same result; a run of n steps is ceil(n / K)
+     * balanced passes, a pass of one step runs mm_closed_kernel. One step reads v of
      * rows x-1..x+1 but f of rows x-2..x+2 (the share of row x+1 needs the count of row
      * x+1, which needs the openness of row x+2). So on a slab with a halo (a chain, any halo
      * mode, MM_SELF_HALO) the engine must have been created with MM_FIELD_HALO=2 or more,
@@ -149,14 +157,18 @@ typedef struct mm_info {
     int steps_per_launch;      /* steps fused per kernel pass (temporal blocking): 1..10
                                   (mm_passk_kernel), 4/8/12/16/20 (mm_wide_kernel, 4/8 for
                                   four-attribute programs), 2..MM_FIELD_MAX_STEPS
-                                  (mm_fieldk_kernel); mixed plans: mm_pass_plan */
+                                  (mm_fieldk_kernel), 2..MM_CLOSED_MAX_STEPS
+                                  (mm_closedk_kernel); mixed plans: mm_pass_plan */
     int kernel;                /* step kernel: 0 one step per pass (mm_pass_kernel, or
                                   mm_field_kernel for a rate-field pass),
                                   2 mm_passk_kernel (steps_per_launch steps per pass, all
                                   levels in one wave), 3 mm_wide_kernel (steps_per_launch
                                   steps per pass, the levels split over 4 waves),
                                   4 mm_fieldk_kernel (steps_per_launch steps of a rate-field
-                                  diffusion per pass; a pass of one step: mm_field_kernel) */
+                                  diffusion per pass; a pass of one step: mm_field_kernel),
+                                  5 mm_closedk_kernel (steps_per_launch steps of a closed
+                                  rate-field diffusion per pass; a pass of one step:
+                                  mm_closed_kernel) */
     int halo_depth;            /* ghost rows one border exchange fills (= steps per pass) */
     int graph_state;           /* 0 no graph used yet, 1 steps replayed as hipGraphs,
                                   -1 stream capture refused: steps run eagerly (graph_note) */
@@ -270,6 +282,11 @@ int mm_device_synchronize(int device);
  * this slab has a neighbour every rate field gets d valid ghost rows, which lets the
  * rate-field passes of a slab with a halo fuse up to d steps; unset, 0, 1 or anything else:
  * 1, one step per pass there),
+ * MM_CLOSED_STEPS (steps per pass of a program that is one closed rate-field diffusion of a
+ * one-attribute engine on a slab without a halo: 2..MM_CLOSED_MAX_STEPS that K on
+ * mm_closedk_kernel, a larger value MM_CLOSED_MAX_STEPS; 0, 1 or unset one step per pass --
+ * there is no default by slab size; with a halo, several attributes, further flows or
+ * MM_PASSK=0 it has no effect),
  * MM_WIDE_COLS (6: every K = 20 pass whose shape allows it -- one attribute, no halo, no step
  * sums in the pass, at least 577 columns -- runs as the fused pass of mm_wide6_kernel, the
  * grid's frame at 4 columns per lane and its interior at 6, whatever the slab's size; 4:

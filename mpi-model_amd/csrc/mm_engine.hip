@@ -35,6 +35,7 @@
 #include "mm_plan.hpp"
 
 static_assert(MM_FIELD_MAX_STEPS == mm::kFieldMaxSteps, "include/mpimodel.h: MM_FIELD_MAX_STEPS");
+static_assert(MM_CLOSED_MAX_STEPS == mm::kClosedMaxSteps, "include/mpimodel.h: MM_CLOSED_MAX_STEPS");
 
 namespace {
 
@@ -282,8 +283,10 @@ bool wring(const mm_engine* e) {
 mm::InstKey inst_key(const mm_engine* e, mm::Kernel kernel, int k, int cols, bool seg, bool red,
                      bool nt) {
     mm::InstKey q{};
-    q.family = kernel == mm::kWide ? mm::kInstWide
-                                   : (kernel == mm::kFieldK ? mm::kInstFieldK : mm::kInstPassK);
+    q.family = kernel == mm::kWide      ? mm::kInstWide
+               : kernel == mm::kFieldK  ? mm::kInstFieldK
+               : kernel == mm::kClosedK ? mm::kInstClosedK
+                                        : mm::kInstPassK;
     q.k = k, q.cols = cols, q.na = e->na;
     q.seg = seg, q.red = red, q.nt = nt;
     if (kernel == mm::kWide && e->na > 1 && e->passes.size() == 1) {
@@ -377,6 +380,10 @@ void sync_program(mm_engine* e) {  // the program's shape, for the planner
     const bool alone = e->na == 1 && p && p->field_mask == 1 && !p->closed && p->diffuse_mask == 0 &&
                        !pin.chains;
     pin.field_k = alone ? mm::field_k_for(pin, field_halo(e)) : 0;
+    // K-step closed passes (mm_closedk_kernel): one attribute, a program that is exactly one
+    // closed diffusion, a slab without a halo, and MM_CLOSED_STEPS asking for them
+    const bool closed_alone = e->na == 1 && p && p->field_mask == 1 && p->closed;
+    pin.closed_k = closed_alone ? mm::closed_k_for(pin, field_halo(e)) : 0;
 }
 
 // Border-row exchange with both neighbours in one RCCL group: the first / last `depth`
@@ -460,7 +467,8 @@ int unsplit_halo(mm_engine* e, int depth) {
 int launch(mm_engine* e, const mm::PassLaunches& pl, bool red, const mm::PassArgs& A, hipStream_t s,
            bool border, bool closed) {
     const int nt = border ? 0 : e->variant;
-    if (pl.kern.kernel != mm::kOneStep)  // mm_passk_kernel, mm_wide_kernel, mm_fieldk_kernel
+    if (pl.kern.kernel != mm::kOneStep)  // mm_passk_kernel, mm_wide_kernel, mm_fieldk_kernel,
+                                         // mm_closedk_kernel
         MM_HIP(mm::launch_kstep(
             inst_key(e, pl.kern.kernel, pl.depth, pl.kern.cols, A.seg != 0, red, nt & 1), A, s));
     else if (closed)  // a closed rate-field pass

@@ -56,6 +56,25 @@ inline long long fieldk_max_rows(int k, long long pitch) {
     return (1LL << 31) / (pitch * 8) - (3 * k + 2 * field_ring(k) + 8);
 }
 
+// mm_closedk_kernel (mm_closedk.hpp): fused steps per closed rate-field pass, K =
+// 2..kClosedMaxSteps (include/mpimodel.h MM_CLOSED_MAX_STEPS).
+constexpr int kClosedMaxSteps = 4;
+// Output columns of its strips. A strip that loads columns [c0, c0 + 128) knows the count of
+// open neighbours only of columns c0+1 .. c0+126, so its level-K values are valid from column
+// c0 + K + 1 on: the discarded halo is floor((K + 2) / 2) lanes, at least K + 1 columns, a side.
+constexpr int closedk_halo_cols(int k) { return 2 * ((k + 2) / 2); }
+constexpr int closedk_out_cols(int k) { return kStripCols - 2 * closedk_halo_cols(k); }
+// Rows of the rate field a wave holds in registers: as field_ring, and the row that runs
+// ahead of level 1 (a row's count needs the openness of the row below it).
+constexpr int closed_ring(int k) {
+    return (kFieldPrefetch + 2 * (k - 1) + 1 + kFieldPrefetch - 1) / kFieldPrefetch * kFieldPrefetch;
+}
+// largest segment (rows) of a K-step closed pass: as fieldk_max_rows, with the rate field one
+// row further ahead
+inline long long closedk_max_rows(int k, long long pitch) {
+    return (1LL << 31) / (pitch * 8) - (3 * k + 2 * closed_ring(k) + 9);
+}
+
 inline bool wide_has(int k, int c, int na) {
     if (na > 1) return na == 4 && c == 2 && (k == 4 || k == 8);
     return c == 4 && (k == 4 || k == 8 || k == 12 || k == 16 || k == 20);

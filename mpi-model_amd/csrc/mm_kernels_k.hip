@@ -1,6 +1,6 @@
 // mm_kernels_k.hip -- the K-step kernels' one table of instances (templates: mm_passk.hpp,
-// mm_wide.hpp and mm_fieldk.hpp; instance units with their lookups: mm_passk_k1..10.hip,
-// mm_wide*.hip, mm_fieldk_k2..4.hip),
+// mm_wide.hpp, mm_fieldk.hpp and mm_closedk.hpp; instance units with their lookups:
+// mm_passk_k1..10.hip, mm_wide*.hip, mm_fieldk_k2..4.hip, mm_closedk_k2..4.hip),
 // their launch, and the fixed-order level-sum finalize kernel.
 #include "mm_wide.hpp"
 
@@ -78,7 +78,8 @@ const KernelInst* find_inst(const InstKey& q) {
         widea_inst_k4,
         widear_inst_k8,    widea8_inst_n1_p0, widea8_inst_n1_p1, widea8_inst_n2_p0,
         widea8_inst_n2_p1, widea8_inst_n3_p0, widea8_inst_n3_p1, widea8_inst_n4_p0,
-        widea8_inst_n4_p1, fieldk_inst_k2,    fieldk_inst_k3,    fieldk_inst_k4};
+        widea8_inst_n4_p1, fieldk_inst_k2,    fieldk_inst_k3,    fieldk_inst_k4,
+        closedk_inst_k2,   closedk_inst_k3,   closedk_inst_k4};
     for (InstLookup unit : kUnits)
         if (const KernelInst* inst = unit(q)) return inst;
     return nullptr;
@@ -96,6 +97,9 @@ hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s) {
     if (q.family == kInstFieldK) {
         if (!a.field[0] || a.field_mask != 1) return hipErrorInvalidValue;
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
+        blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
+    } else if (q.family == kInstClosedK) {
+        if (!a.field[0] || a.field_mask != 1 || !q.seg) return hipErrorInvalidValue;
         blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
     } else if (q.family == kInstPassK) {
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;

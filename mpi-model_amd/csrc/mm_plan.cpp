@@ -49,6 +49,8 @@ const KnobRow kKnobRows[] = {
     {"MM_KERNEL_VARIANT", 'i', 0, kAny, [](Knobs& k, double v) { k.variant = (int)std::min(v, 1e9); }},
     {"MM_FIELD_STEPS", 'i', 0, kFieldMaxSteps, [](Knobs& k, double v) { k.field_steps = (int)v; }},
     {"MM_FIELD_HALO", 'i', 1, kFieldMaxSteps, [](Knobs& k, double v) { k.field_halo = (int)v; }},
+    {"MM_CLOSED_STEPS", 'i', 0, kAny,
+     [](Knobs& k, double v) { k.closed_steps = (int)std::min(v, (double)kClosedMaxSteps); }},
     {"MM_WIDE_COLS", 'i', 4, kWide6Cols, [](Knobs& k, double v) { if (v != 5) k.wide_cols = (int)v; }},
 };
 
@@ -212,6 +214,9 @@ double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
     // mm_fieldk_kernel: the general body adds a short division per edge cell and keeps the
     // levels interleaved; full-length edge segments until a measurement says otherwise
     if (kernel == kFieldK) return 1.0;
+    // mm_closedk_kernel chooses its body from the data, row by row, in every strip alike:
+    // full-length edge segments, not measured otherwise
+    if (kernel == kClosedK) return 1.0;
     if (kernel == kWide) return in.n_attr == 1 ? 1.0 : 0.5;
     if (k >= 10) return 0.1;
     if (k == 9) return 0.2;
@@ -221,6 +226,7 @@ double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
 long long waves_for(long long nstrips, long long n, int th) { return n <= 0 ? 0 : nstrips * ceil_div(n, th); }
 
 bool fieldk_on(const PlanIn& in) { return in.field_k >= 2 && !in.closed; }
+bool closedk_on(const PlanIn& in) { return in.closed_k >= 2 && in.closed; }
 
 // MM_FIELD_STEPS unset: K = kFieldAutoSteps on slabs of at least kFieldAutoCells cells
 // (the table of tools/bench_field.py: the built K of the best time per step
@@ -257,7 +263,15 @@ int field_k_for(const PlanIn& in, bool halo) {
     return k >= 2 ? k : 0;
 }
 
-bool kstep_ok(const PlanIn& in) { return fieldk_on(in) || passk_ok(in); }
+int closed_k_for(const PlanIn& in, bool halo) {
+    const int k = std::min(in.knobs.closed_steps, kClosedMaxSteps);
+    if (halo || !in.closed || !in.knobs.passk || k < 2 || in.pitch <= 0 ||
+        closedk_max_rows(kClosedMaxSteps, in.pitch) < 64)
+        return 0;
+    return k;
+}
+
+bool kstep_ok(const PlanIn& in) { return fieldk_on(in) || closedk_on(in) || passk_ok(in); }
 
 bool passk_ok(const PlanIn& in) {
     if (!in.knobs.passk || in.n_passes != 1 || in.field) return false;
@@ -282,6 +296,8 @@ namespace {
 KernelChoice kernel4_for(const PlanIn& in, int k) {
     // a rate-field program in K-step passes: a pass of one step stays on mm_field_kernel
     if (fieldk_on(in) && k >= 2) return {kFieldK, 2, ceil_div(in.W, passk_out_cols(k))};
+    // and a closed program's on mm_closed_kernel
+    if (closedk_on(in) && k >= 2) return {kClosedK, 2, ceil_div(in.W, closedk_out_cols(k))};
     if (!passk_ok(in)) return {kOneStep, 1, 0};  // one mm_pass_kernel launch per pass of the step
     if (use_wide(in, k)) return {kWide, wcols(in), ceil_div(in.W, wide_out_cols(k, wcols(in)))};
     return {kPassK, 2, ceil_div(in.W, passk_out_cols(k))};
@@ -299,6 +315,7 @@ KernelChoice kernel_for(const PlanIn& in, int k, bool red) {
 
 int steps_per_launch(const PlanIn& in) {
     if (fieldk_on(in)) return in.field_k;
+    if (closedk_on(in)) return in.closed_k;
     return passk_ok(in) ? passk_steps(in) : 1;
 }
 
@@ -311,6 +328,7 @@ int steps_per_launch(const PlanIn& in) {
 int next_pass_len(const PlanIn& in, long long n) {
     // a rate-field program: ceil(n / K) balanced passes (7 steps at K = 4: 4 + 3)
     if (fieldk_on(in)) return (int)ceil_div(n, ceil_div(n, in.field_k));
+    if (closedk_on(in)) return (int)ceil_div(n, ceil_div(n, in.closed_k));  // the same
     if (!passk_ok(in)) return 1;
     const Knobs& kn = in.knobs;
     const int kp = passk_steps(in);
@@ -368,7 +386,9 @@ long long seg_wave_count(long long n, long long ns, long long r, long long re) {
 // kernel's occupancy x CUs).
 Segments segments(const PlanIn& in, Kernel kernel, int k, int slots, long long n, long long ns) {
     const long long maxr = std::max<long long>(
-        16, kernel == kFieldK ? fieldk_max_rows(k, in.pitch) : passk_max_rows(k, in.pitch));
+        16, kernel == kFieldK    ? fieldk_max_rows(k, in.pitch)
+            : kernel == kClosedK ? closedk_max_rows(k, in.pitch)
+                                 : passk_max_rows(k, in.pitch));
     const double edge = seg_edge_of(in, kernel, k);
     const double units = ns < 3 ? (double)ns / edge : (double)(ns - 2) + 2.0 / edge;
     // even segment lengths: with an even first row (x_init and lo even, as every bench
@@ -572,7 +592,8 @@ long long partials_need(const PlanIn& in) {
     // plus 4-row border blocks (depth <= kGhost rows on each side) with K x NA sums per
     // wave: K <= kMaxSteps for one attribute, K <= 2 for up to kMaxAttr; mm_fieldk_kernel,
     // segments of >= 8 rows over no more strips than these plus, split, one 4-row border
-    // block per strip and side, K <= kFieldMaxSteps sums per wave
+    // block per strip and side, K <= kFieldMaxSteps sums per wave; mm_closedk_kernel, segments
+    // of >= 8 rows over fewer strips still (closedk_out_cols), K <= kClosedMaxSteps sums per wave
     const long long ns1 = in.pitch / kStripCols;
     const long long need = (waves_for(ns1, in.h, 8) + 2 * waves_for(ns1, 2, 1) + 16) * kMaxAttr;
     const long long ns = ceil_div(in.W, passk_out_cols(kMaxSteps));

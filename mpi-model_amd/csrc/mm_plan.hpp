@@ -41,13 +41,16 @@ struct Knobs {
     int field_halo = 1;      // valid ghost rows of every rate field on each side that has a
                              // neighbour, the caller's promise (MM_FIELD_HALO, 1..kFieldMaxSteps):
                              // bounds the K of a rate-field pass on a slab with a halo
+    int closed_steps = 0;    // steps per closed rate-field pass (MM_CLOSED_STEPS: 0 or 1 one step
+                             // per pass, 2..kClosedMaxSteps that K on mm_closedk_kernel; no
+                             // auto rule)
     int wide_cols = 0;       // MM_WIDE_COLS: 6 the fused six-column K = 20 pass wherever its
                              // shape allows (wide6_on), 4 never; 0 auto: slabs of >= 2^27 cells
 };
 // `get` is std::getenv or a stand-in for it.
 Knobs read_knobs(const std::function<const char*(const char*)>& get);
 
-enum Kernel { kOneStep = 0, kPassK = 2, kWide = 3, kFieldK = 4 };  // mm_info.kernel's numbers
+enum Kernel { kOneStep = 0, kPassK = 2, kWide = 3, kFieldK = 4, kClosedK = 5 };  // mm_info.kernel's numbers
 
 struct PlanIn {
     long long H = 0, W = 0, h = 0, x_init = 0;
@@ -64,13 +67,17 @@ struct PlanIn {
     bool field = false;      // some pass is a rate-field pass (mm_field_kernel): one step per pass
     bool closed = false;     // some pass is a closed rate-field pass (mm_closed_kernel): field is
                              // set too, and the program stays at one step per pass, halo depth
-                             // 1, whatever MM_FIELD_STEPS / MM_FIELD_HALO say (field_k_for: 0)
+                             // 1, whatever MM_FIELD_STEPS / MM_FIELD_HALO say (field_k_for: 0),
+                             // unless closed_k says otherwise
     int field_k = 0;         // >= 2: the program is one rate-field diffusion of one attribute,
                              // and its passes fuse up to this many steps on mm_fieldk_kernel
                              // (the engine sets field_k_for; 0: off)
+    int closed_k = 0;        // >= 2: the program is one closed rate-field diffusion of one
+                             // attribute on a slab without a halo, and its passes fuse up to this
+                             // many steps on mm_closedk_kernel (the engine sets closed_k_for; 0: off)
     Knobs knobs;
     int ncu = 0;             // compute units of the device
-    // resident wave (kPassK, kFieldK) or workgroup (kWide) slots per CU of the instance that runs a
+    // resident wave (kPassK, kFieldK, kClosedK) or workgroup (kWide) slots per CU of the instance that runs a
     // pass of k steps, with the step sums or without: the one plan input the device gives
     std::function<int(Kernel, int k, bool red)> slots;
     // workgroup slots per CU of the fused six-column instance of k steps (mm_wide6_kernel);
@@ -86,7 +93,7 @@ struct KernelChoice {
 
 struct Segments {
     int th, th_edge;   // rows per interior-strip and per edge-strip segment
-    long long count;   // waves (kPassK, kFieldK) or workgroups (kWide)
+    long long count;   // waves (kPassK, kFieldK, kClosedK) or workgroups (kWide)
 };
 
 // The fused six-column pass (mm_wide.hpp mm_wide6_kernel), one launch of rows [lo, hi) = the
@@ -135,7 +142,13 @@ int field_steps_for(const PlanIn& in);
 // engine never exchanges and the caller promises; under 2: 0. A program with a closed
 // diffusion (in.closed): 0.
 int field_k_for(const PlanIn& in, bool halo);
-// A run advances in K-step passes of the program's only pass: passk_ok, or field_k >= 2.
+// PlanIn::closed_k of a program that may run on mm_closedk_kernel (one attribute, exactly one
+// closed diffusion -- the engine checks that): min(MM_CLOSED_STEPS, kClosedMaxSteps) where that
+// is 2 or more; 0 (one step per pass) with the knob unset, 0 or 1, with a halo (a chain, any
+// halo mode, MM_SELF_HALO), under MM_PASSK=0 and where closedk_max_rows < 64. No auto rule.
+int closed_k_for(const PlanIn& in, bool halo);
+// A run advances in K-step passes of the program's only pass: passk_ok, field_k >= 2 or
+// closed_k >= 2.
 bool kstep_ok(const PlanIn& in);
 // red: the pass sums some of its steps (only the choice of the six-column pass depends on it)
 KernelChoice kernel_for(const PlanIn& in, int k, bool red = false);

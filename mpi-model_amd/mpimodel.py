@@ -20,6 +20,7 @@ MM_FLOW_TRANSFER = 2
 MM_FLOW_DIFFUSE_FIELD = 3
 MM_FLOW_DIFFUSE_CLOSED = 4
 FIELD_MAX_STEPS = 4  # MM_FIELD_MAX_STEPS: most steps mm_fieldk_kernel fuses per pass (MM_FIELD_STEPS)
+CLOSED_MAX_STEPS = 4  # MM_CLOSED_MAX_STEPS: most steps mm_closedk_kernel fuses per pass (MM_CLOSED_STEPS)
 MM_FILL_UNIFORM = 0
 MM_FILL_RANDOM = 1
 MM_HALO_NONE = 0
@@ -371,7 +372,8 @@ class Engine:
 
     def pass_kernel(self, k):
         """(kernel, columns per lane, strips) of a k-step pass (mm_pass_kernel): kernel 0 =
-        mm_pass_kernel, 2 = mm_passk_kernel, 3 = mm_wide_kernel."""
+        mm_pass_kernel, 2 = mm_passk_kernel, 3 = mm_wide_kernel, 4 = mm_fieldk_kernel,
+        5 = mm_closedk_kernel."""
         kern, cols, strips = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
         check(lib().mm_pass_kernel(self.ptr, k, ctypes.byref(kern), ctypes.byref(cols),
                                    ctypes.byref(strips)))

@@ -27,8 +27,14 @@ of the K arms: `field`, the one-step field pass as the baseline of the same run;
 same engine shape and the same mm_rate_field_fill(0.1) field, every cell open (the ballot
 takes the division-free body on every interior row); `closed_disc`, that field with a disc
 of walls of about a quarter of the grid in its middle (rows that cross the disc's rim run the
-general body, rows inside it the body of rows in which nothing emits). The summary's
-bytes_ratio is the all-open closed pass's bytes/s over the field pass's (target: >= 0.9).
+general body, rows inside it the body of rows in which nothing emits); `closed2` ..
+`closedK` and `closed2_disc` .. `closedK_disc`, the K-step closed pass (mm_closedk_kernel,
+MM_CLOSED_STEPS=K) for every built K on those two fields; and `field2` .. `fieldK`, the K-step
+field pass of the same run. The summary's bytes_ratio is the all-open closed pass's bytes/s
+over the field pass's (target: >= 0.9); a K arm's x_one_step is its time per step over the
+one-step closed arm's of the same field (`closed` / `closed_disc`), beats_one_step whether it
+was below it in every round, pass_x its time per pass over that arm's, and over_fieldk the
+all-open pass's time over the field kind's pass of the same K.
 
 Every arm times at least --steps steps, rounded up to a multiple of its K. Prints one JSON
 line per arm and round, then per size a summary line. For the K arms the summary holds the
@@ -52,6 +58,7 @@ import mpimodel as mm  # noqa: E402
 mm.lib()
 PEAK = 8e12  # B/s, MI355X HBM3E
 KS = list(range(2, mm.FIELD_MAX_STEPS + 1))
+CLOSED_KS = list(range(2, mm.CLOSED_MAX_STEPS + 1))
 
 
 def out_cols(k):
@@ -90,15 +97,17 @@ def engine(H, W, k, self_halo=False):
     return e
 
 
-def closed_engine(H, W, disc):
-    """The closed pass on the field of the `field` arm; disc: a disc of walls of a quarter of
-    the grid's cells in the middle."""
+def closed_engine(H, W, disc, k=1):
+    """The closed pass on the field of the `field` arm, k steps per pass; disc: a disc of walls
+    of a quarter of the grid's cells in the middle."""
     old = {name: os.environ.pop(name, None) for name in ("MM_PASSK", "MM_FIELD_STEPS", "MM_SELF_HALO",
-                                                         "MM_FIELD_HALO")}
+                                                         "MM_FIELD_HALO", "MM_CLOSED_STEPS")}
     try:
+        os.environ["MM_CLOSED_STEPS"] = str(k)
         e = mm.Engine(H, W)
     finally:
-        os.environ.update({k: v for k, v in old.items() if v is not None})
+        os.environ.pop("MM_CLOSED_STEPS", None)
+        os.environ.update({name: v for name, v in old.items() if v is not None})
     e.fill_random(0)
     e.rate_field_fill(0.1)
     if disc:
@@ -111,7 +120,8 @@ def closed_engine(H, W, disc):
             e.rate_field_upload(np.where(x[:, None] + y[None, :] <= r2, 0.0, 0.1), row0=x0)
     e.add_diffuse_closed(0)
     info = e.info()
-    assert (info["kernel"], info["steps_per_launch"], info["n_passes"]) == (0, 1, 1), info
+    want = (5, k, 1) if k >= 2 else (0, 1, 1)
+    assert (info["kernel"], info["steps_per_launch"], info["n_passes"]) == want, info
     return e
 
 
@@ -120,10 +130,18 @@ def run_closed(size, a):
     H, W = shape_of(size)
     engines = {"field": engine(H, W, 1), "closed": closed_engine(H, W, False),
                "closed_disc": closed_engine(H, W, True)}
+    arms = {name: 1 for name in engines}
+    for k in CLOSED_KS:
+        engines["closed%d" % k] = closed_engine(H, W, False, k)
+        engines["closed%d_disc" % k] = closed_engine(H, W, True, k)
+        arms["closed%d" % k] = arms["closed%d_disc" % k] = k
+        if k in KS:
+            engines["field%d" % k] = engine(H, W, k)
+            arms["field%d" % k] = k
     res = {name: [] for name in engines}
     for rnd in range(a.rounds):
         for name, e in engines.items():
-            r = measure(e, H * W, 1, a.warmup, a.steps)
+            r = measure(e, H * W, arms[name], a.warmup, a.steps)
             res[name].append(r)
             print(json.dumps({"arm": name, "round": rnd, "H": H, "W": W, **r}), flush=True)
     for e in engines.values():
@@ -135,8 +153,21 @@ def run_closed(size, a):
            "target_met": min(ratios) >= 0.9, "arms": {}}
     for name, rows in res.items():
         out["arms"][name] = {key: span(rows, key) for key in
-                             ("pass_us", "wall_step_us", "GCUPS", "bytes_per_cell_update", "TBps",
-                              "of_peak")}
+                             ("pass_us", "step_us", "wall_step_us", "GCUPS", "bytes_per_cell_update",
+                              "TBps", "of_peak")}
+    for k in CLOSED_KS:
+        for tail in ("", "_disc"):
+            name, one = "closed%d%s" % (k, tail), "closed" + tail
+            arm = out["arms"][name]
+            arm["x_one_step"] = round(arm["step_us"]["mean"] / out["arms"][one]["step_us"]["mean"], 3)
+            arm["pass_x"] = round(arm["pass_us"]["mean"] / out["arms"][one]["pass_us"]["mean"], 3)
+            # faster per step than the one-step closed pass of the same round, in every round
+            arm["beats_one_step"] = all(r["step_us"] < c["step_us"]
+                                        for r, c in zip(res[name], res[one]))
+        if "field%d" % k in res:
+            out["arms"]["closed%d" % k]["over_fieldk"] = round(
+                out["arms"]["closed%d" % k]["pass_us"]["mean"] /
+                out["arms"]["field%d" % k]["pass_us"]["mean"], 3)
     print(json.dumps(out), flush=True)
     return out
 
@@ -249,16 +280,17 @@ def run_size(size, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="2048,4096,8192,16384")
-    ap.add_argument("--size", default="", help="one size (instead of --sizes)")
+    ap.add_argument("--size", default="", help="one size or several (instead of --sizes)")
     ap.add_argument("--self-halo", action="store_true",
                     help="MM_HALO_RCCL + MM_SELF_HALO=1 + MM_FIELD_HALO=4: the split schedule")
     ap.add_argument("--closed", action="store_true",
-                    help="the closed pass (all open, and around a disc of walls) beside the field pass")
+                    help="the closed pass, one step and K steps per pass (all open, and around a "
+                         "disc of walls), beside the field pass")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
-    sizes = [a.size] if a.size else a.sizes.split(",")
+    sizes = (a.size or a.sizes).split(",")
     cells = lambda s: shape_of(s)[0] * shape_of(s)[1]  # noqa: E731
     if a.closed:
         for size in sizes:
