@@ -17,7 +17,9 @@
 //   * per-step sums (MPI_Report) are reduced on the device into a growable history.
 // This unit runs: streams, events, graph capture, RCCL and the launches. What a run does --
 // kernel per pass, pass lengths, segments, launches, graph length, the MM_* knobs -- is
-// planned in mm_plan.cpp (host-only) from the engine's mm::PlanIn.
+// planned in mm_plan.cpp (host-only) from the engine's mm::PlanIn; what the flow list means --
+// its fused passes, the ring, the program's shape in that PlanIn -- is mm_program.cpp's
+// (host-only too).
 // The reference's per-worker body this replaces is src/Model.hpp:135-261.
 #include <rccl/rccl.h>
 
@@ -33,6 +35,7 @@
 #include "../../include/mpimodel.h"
 #include "mm_inst.hpp"
 #include "mm_plan.hpp"
+#include "mm_program.hpp"
 
 static_assert(MM_FIELD_MAX_STEPS == mm::kFieldMaxSteps, "include/mpimodel.h: MM_FIELD_MAX_STEPS");
 static_assert(MM_CLOSED_MAX_STEPS == mm::kClosedMaxSteps, "include/mpimodel.h: MM_CLOSED_MAX_STEPS");
@@ -66,28 +69,6 @@ int fail(int code, const std::string& msg) {
         if (rc_ != MM_OK) return rc_; \
     } while (0)
 
-struct Transfer {
-    int a, b;
-    double rate;
-};
-
-// A fused pass: pre-chain transfers, at most one diffusion per attribute, post-chain. A
-// rate-field pass (field_mask != 0) holds field diffusions of distinct attributes only.
-struct Pass {
-    std::vector<Transfer> pre, post;
-    int diffuse_mask = 0;
-    double drate[mm::kMaxAttr] = {0, 0, 0, 0};
-    int field_mask = 0;
-    // a closed rate-field diffusion (MM_FLOW_DIFFUSE_CLOSED, mm_closed_kernel): the pass holds
-    // that one flow alone, field_mask its attribute's bit
-    bool closed = false;
-};
-
-struct FlowDesc {
-    int kind, a, b;
-    double rate;
-};
-
 }  // namespace
 
 struct mm_engine {
@@ -114,13 +95,13 @@ struct mm_engine {
     bool comm_live = false;  // border work of this run is pending on the comm stream
     ncclComm_t comm = nullptr;
 
-    std::vector<FlowDesc> flows;
-    std::vector<Pass> passes;
+    std::vector<mm::Flow> flows;
+    std::vector<mm::Pass> passes;  // mm::compile_passes(flows)
 
     mm::PlanIn pin;  // what the planner sees of the engine (mm_plan.hpp): slab, program shape,
                      // the MM_* knobs, the device; pin.split: interior / border split
     int th_env = 8;  // MM_ROWS_PER_WAVE as the environment asked; pin.knobs.th is the
-                     // effective height, derived from it and the program (sync_program)
+                     // effective height, derived from it and the program (mm::set_program)
     std::map<const mm::KernelInst*, int> slots;  // occupancy cache (slots_per_cu)
     bool self_halo = false;  // test mode: one RCCL rank exchanges border rows with itself
     int variant = 0;  // kernel tuning variant (MM_KERNEL_VARIANT), 0 = default
@@ -166,66 +147,7 @@ void drop_graphs(mm_engine* e) {
     e->graphs.clear();
 }
 
-int compile_passes(mm_engine* e) {
-    e->passes.clear();
-    Pass cur;
-    bool open = false;
-    for (const FlowDesc& f : e->flows) {
-        // a closed diffusion is a pass of its own: it closes any open pass and shares its
-        // own with nothing
-        if (f.kind == MM_FLOW_DIFFUSE_CLOSED) {
-            if (open) e->passes.push_back(cur);
-            open = false;
-            Pass c;
-            c.field_mask = 1 << f.a;
-            c.closed = true;
-            e->passes.push_back(c);
-            continue;
-        }
-        // rate-field diffusions get passes of their own: consecutive ones of distinct
-        // attributes share a pass; any other flow closes it, and they close any other pass
-        const bool fieldf = f.kind == MM_FLOW_DIFFUSE_FIELD;
-        if (open && (fieldf ? (!cur.field_mask || (cur.field_mask & (1 << f.a))) : cur.field_mask != 0)) {
-            e->passes.push_back(cur);
-            open = false;
-        }
-        if (fieldf) {
-            if (!open) {
-                cur = Pass();
-                open = true;
-            }
-            cur.field_mask |= 1 << f.a;
-        } else if (f.kind == MM_FLOW_TRANSFER) {
-            if (!open) {
-                cur = Pass();
-                open = true;
-            }
-            std::vector<Transfer>& chain = cur.diffuse_mask ? cur.post : cur.pre;
-            if ((int)chain.size() >= mm::kMaxChain) {
-                e->passes.push_back(cur);
-                cur = Pass();
-                cur.pre.push_back({f.a, f.b, f.rate});
-            } else {
-                chain.push_back({f.a, f.b, f.rate});
-            }
-        } else {  // MM_FLOW_DIFFUSE
-            if (!open) {
-                cur = Pass();
-                open = true;
-            }
-            if ((cur.diffuse_mask & (1 << f.a)) || !cur.post.empty()) {
-                e->passes.push_back(cur);
-                cur = Pass();
-            }
-            cur.diffuse_mask |= 1 << f.a;
-            cur.drate[f.a] = f.rate;
-        }
-    }
-    if (open) e->passes.push_back(cur);
-    return MM_OK;
-}
-
-void fill_args(const mm_engine* e, const Pass& p, mm::PassArgs& A) {
+void fill_args(const mm_engine* e, const mm::Pass& p, mm::PassArgs& A) {
     std::memset(&A, 0, sizeof A);
     for (int a = 0; a < e->na; ++a) {
         A.in[a] = e->buf[e->cur][a];
@@ -263,18 +185,6 @@ hipEvent_t next_event(mm_engine* e) {
     return e->ev_pool[e->ev_used++];
 }
 
-// A one-pass program of four attributes whose pre-chain is the ring of transfers t -> t+1
-// mod 4 in that order, without a post-chain (config C5's topology), runs the wide instance
-// with the chain's operands fixed at compile time.
-bool wring(const mm_engine* e) {
-    if (!e->pin.knobs.ring_ok || e->na != 4 || e->passes.size() != 1) return false;
-    const Pass& p = e->passes[0];
-    if ((int)p.pre.size() != e->na || !p.post.empty() || p.diffuse_mask != 15) return false;
-    for (int t = 0; t < e->na; ++t)
-        if (p.pre[t].a != t || p.pre[t].b != (t + 1) % e->na) return false;
-    return true;
-}
-
 // The key of the instance that runs a k-step pass of the engine's program (mm_inst.hpp).
 // nt: non-temporal stores -- bit 0 of the tuning variant and no other bit of it, so no user
 // value of MM_KERNEL_VARIANT selects the ring instance. A four-attribute wide pass adds what
@@ -290,8 +200,8 @@ mm::InstKey inst_key(const mm_engine* e, mm::Kernel kernel, int k, int cols, boo
     q.k = k, q.cols = cols, q.na = e->na;
     q.seg = seg, q.red = red, q.nt = nt;
     if (kernel == mm::kWide && e->na > 1 && e->passes.size() == 1) {
-        const Pass& p = e->passes[0];
-        q.ring = wring(e);
+        const mm::Pass& p = e->passes[0];
+        q.ring = e->pin.ring;
         q.post = !p.post.empty();
         q.nd = __builtin_popcount((unsigned)p.diffuse_mask);
     }
@@ -308,7 +218,7 @@ constexpr int kPermIdentity = 0 | 1 << 2 | 2 << 4 | 3 << 6;
 // sums (partials come out in physical order; the history is logical).
 int relabel(const mm_engine* e, mm::PassArgs& A) {
     if (e->na == 1) return kPermIdentity;
-    const Pass& p = e->passes[0];
+    const mm::Pass& p = e->passes[0];
     int perm[mm::kMaxAttr], inv[mm::kMaxAttr], n = 0;
     for (int a = 0; a < e->na; ++a)
         if ((p.diffuse_mask >> a) & 1) perm[n++] = a;
@@ -353,37 +263,10 @@ int slots_per_cu(mm_engine* e, mm::Kernel kernel, int k, bool red, int cols = 0)
 // The slab has a halo: a neighbour, or a halo mode on one slab (the self-halo among them).
 bool field_halo(const mm_engine* e) { return e->d.nranks > 1 || e->d.halo_mode != MM_HALO_NONE; }
 
-void sync_program(mm_engine* e) {  // the program's shape, for the planner
-    mm::PlanIn& pin = e->pin;
-    pin.n_passes = (int)e->passes.size();
-    const Pass* p = pin.n_passes == 1 ? &e->passes[0] : nullptr;
-    pin.diffuse_mask = p ? p->diffuse_mask : 0;
-    pin.chains = p && !(p->pre.empty() && p->post.empty());
-    pin.ring = wring(e);
-    pin.field = pin.closed = false;
-    for (const Pass& q : e->passes) {
-        pin.field = pin.field || q.field_mask != 0;
-        pin.closed = pin.closed || q.closed;  // one step per pass, whatever the knobs say
-    }
-    // transfers, several attributes or a rate field: those kernels exist for 8-row blocks
-    // only. Any other program, the empty one included, gets the height the environment asked
-    // for back: a reprogrammed engine plans as a fresh one (include/mpimodel.h, mm_clear_flows)
-    bool eight = e->na > 1;
-    for (const Pass& q : e->passes)
-        eight = eight || !q.pre.empty() || !q.post.empty() || q.field_mask != 0;
-    pin.knobs.th = eight ? 8 : e->th_env;
-    // K-step rate-field passes (mm_fieldk_kernel): one attribute and a program that is
-    // exactly one field diffusion (further attributes would need a copy). With a halo -- a
-    // chain, a self-halo, any halo mode -- K is also bounded by the ghost rows of the field
-    // the caller promised at creation (MM_FIELD_HALO, 1 unless set: one step per pass) and by
-    // the chain's thinnest slab; whether the rows are there is check_run's business.
-    const bool alone = e->na == 1 && p && p->field_mask == 1 && !p->closed && p->diffuse_mask == 0 &&
-                       !pin.chains;
-    pin.field_k = alone ? mm::field_k_for(pin, field_halo(e)) : 0;
-    // K-step closed passes (mm_closedk_kernel): one attribute, a program that is exactly one
-    // closed diffusion, a slab without a halo, and MM_CLOSED_STEPS asking for them
-    const bool closed_alone = e->na == 1 && p && p->field_mask == 1 && p->closed;
-    pin.closed_k = closed_alone ? mm::closed_k_for(pin, field_halo(e)) : 0;
+// After every change of the flow list: its passes, and the program's shape for the planner.
+void set_program(mm_engine* e) {
+    e->passes = mm::compile_passes(e->flows);
+    mm::set_program(e->pin, e->passes, field_halo(e), e->th_env);
 }
 
 // Border-row exchange with both neighbours in one RCCL group: the first / last `depth`
@@ -502,7 +385,7 @@ void set_launch(mm::PassArgs& A, const mm::Launch& l) {
 // priming mark waves_a < 0), no exchange, no state change. A split pass also launches on
 // the comm stream, another queue with its own scratch: unprimed, the first border launch of
 // a 20-step run blocked the host for 1.5 ms (8192 x 32768 self-halo, profiles/r06/trace20).
-int enqueue_pass(mm_engine* e, const Pass& p, int k, int mask, bool time_it, bool prime = false) {
+int enqueue_pass(mm_engine* e, const mm::Pass& p, int k, int mask, bool time_it, bool prime = false) {
     const bool red = mask != 0;
     const mm::PassLaunches pl = mm::pass_launches(e->pin, k, red);
     mm::PassArgs A;
@@ -930,7 +813,7 @@ int mm_engine_info(mm_engine* e, mm_info* info) {
     info->waves_per_pass = sp.waves_per_pass;
     info->seg_waves_per_cu = sp.seg_waves_per_cu;
     if (sp.kernel == mm::kWide && e->na > 1)
-        info->chain_kernel = (wring(e) && sp.steps_per_launch == 8) ? MM_CHAIN_RING : MM_CHAIN_RUNTIME;
+        info->chain_kernel = (e->pin.ring && sp.steps_per_launch == 8) ? MM_CHAIN_RING : MM_CHAIN_RUNTIME;
     info->steps_done = e->steps_done;
     info->fused_attrs = e->na;
     info->steps_per_launch = info->halo_depth = sp.steps_per_launch;
@@ -980,8 +863,7 @@ int mm_clear_flows(mm_engine* e) {
     MM_TRY(set_device(e));
     MM_HIP(hipStreamSynchronize(e->s_comp));
     e->flows.clear();
-    e->passes.clear();
-    sync_program(e);
+    set_program(e);
     drop_graphs(e);
     return MM_OK;
 }
@@ -1001,8 +883,7 @@ int mm_add_flow(mm_engine* e, int kind, int a, int b, double rate) {
     MM_HIP(hipStreamSynchronize(e->s_comp));
     e->flows.push_back({kind, a, kind == MM_FLOW_TRANSFER ? (b < 0 ? -1 : b) : a, rate});
     drop_graphs(e);
-    MM_TRY(compile_passes(e));
-    sync_program(e);
+    set_program(e);
     return MM_OK;
 }
 
@@ -1105,11 +986,33 @@ int mm_point_apply_strict(mm_engine* e, int attr, long long sx, long long sy, do
 
 namespace {
 
+// The field of attribute a holds the `depth` ghost rows that `reader` (the message's subject)
+// reads on every side with a real neighbour, clipped to the grid; knob: how the caller
+// promised them.
+int check_field_rows(mm_engine* e, const char* who, int a, long long depth, const char* reader,
+                     const char* knob) {
+    const long long want[2] = {e->d.rank > 0 ? std::min<long long>(depth, e->d.x_init) : 0,
+                               e->d.rank < e->d.nranks - 1
+                                   ? std::min<long long>(depth, e->d.H - e->d.x_init - e->d.h)
+                                   : 0};
+    for (int side = 0; side < 2; ++side)
+        if (e->fld_rows[a][side] < want[side]) {
+            char msg[256];
+            std::snprintf(msg, sizeof msg,
+                          "%s: %s %lld ghost rows of the field of attribute %d %s the slab (%s), "
+                          "%lld have been uploaded (mm_rate_field_upload / mm_rate_field_fill)",
+                          who, reader, want[side], a, side == 0 ? "above" : "below", knob,
+                          e->fld_rows[a][side]);
+            return fail(MM_ERR_STATE, msg);
+        }
+    return MM_OK;
+}
+
 int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char* who) {
     if (!e || nsteps < 0 || reduce_every < 0) return fail(MM_ERR_INVALID, std::string(who) + ": bad arguments");
     if (nsteps == 0) return MM_OK;
     if (e->passes.empty()) return fail(MM_ERR_STATE, std::string(who) + ": no flow added (mm_add_flow)");
-    for (const Pass& p : e->passes)
+    for (const mm::Pass& p : e->passes)
         for (int a = 0; a < e->na; ++a)
             if (((p.field_mask >> a) & 1) && !e->fld[a])
                 return fail(MM_ERR_STATE, std::string(who) + ": a rate-field diffusion's attribute has "
@@ -1118,48 +1021,21 @@ int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char
     // side that has a real neighbour (a self-halo side has none: its ghost rows lie outside
     // the grid). The engine never exchanges the field: the caller promised the rows at
     // creation (MM_FIELD_HALO), and a run without them is refused before it leaves a trace.
-    if (e->pin.field_k >= 2 && field_halo(e)) {
-        const long long depth = mm::steps_per_launch(e->pin);
-        const long long want[2] = {e->d.rank > 0 ? std::min<long long>(depth, e->d.x_init) : 0,
-                                   e->d.rank < e->d.nranks - 1
-                                       ? std::min<long long>(depth, e->d.H - e->d.x_init - e->d.h)
-                                       : 0};
-        for (int side = 0; side < 2; ++side)
-            if (e->fld_rows[0][side] < want[side]) {
-                char msg[256];
-                std::snprintf(msg, sizeof msg,
-                              "%s: K-step rate-field passes read %lld ghost rows of the field of "
-                              "attribute 0 %s the slab (MM_FIELD_HALO), %lld have been uploaded "
-                              "(mm_rate_field_upload / mm_rate_field_fill)",
-                              who, want[side], side == 0 ? "above" : "below", e->fld_rows[0][side]);
-                return fail(MM_ERR_STATE, msg);
-            }
-    }
+    if (e->pin.field_k >= 2 && field_halo(e))
+        MM_TRY(check_field_rows(e, who, 0, mm::steps_per_launch(e->pin),
+                                "K-step rate-field passes read", "MM_FIELD_HALO"));
     // A closed pass counts open neighbours: the share of the neighbour's border row needs
     // that row's count, which reads the field one row further out. On a slab with a halo the
     // caller promises two ghost rows of the field at creation (MM_FIELD_HALO=2) and uploads
     // them on every side with a real neighbour; the plan itself never depends on either.
-    for (const Pass& p : e->passes) {
+    for (const mm::Pass& p : e->passes) {
         if (!p.closed || !field_halo(e)) continue;
-        const int a = __builtin_ctz((unsigned)p.field_mask);
         if (e->pin.knobs.field_halo < 2)
             return fail(MM_ERR_STATE, std::string(who) + ": a closed diffusion on a slab with a halo "
                                       "reads two ghost rows of the field: create the engine with "
                                       "MM_FIELD_HALO=2 (or more) and upload rows -2..h+1");
-        const long long want[2] = {e->d.rank > 0 ? std::min<long long>(2, e->d.x_init) : 0,
-                                   e->d.rank < e->d.nranks - 1
-                                       ? std::min<long long>(2, e->d.H - e->d.x_init - e->d.h)
-                                       : 0};
-        for (int side = 0; side < 2; ++side)
-            if (e->fld_rows[a][side] < want[side]) {
-                char msg[256];
-                std::snprintf(msg, sizeof msg,
-                              "%s: a closed diffusion reads %lld ghost rows of the field of "
-                              "attribute %d %s the slab (MM_FIELD_HALO=2), %lld have been uploaded "
-                              "(mm_rate_field_upload / mm_rate_field_fill)",
-                              who, want[side], a, side == 0 ? "above" : "below", e->fld_rows[a][side]);
-                return fail(MM_ERR_STATE, msg);
-            }
+        MM_TRY(check_field_rows(e, who, __builtin_ctz((unsigned)p.field_mask), 2,
+                                "a closed diffusion reads", "MM_FIELD_HALO=2"));
     }
     if (e->d.halo_mode == MM_HALO_HOST && e->d.nranks > 1) {
         if (e->passes.size() != 1)

@@ -199,6 +199,32 @@ int wide_plan_first(const PlanIn& in, long long n, int kcap) {
     return first[(size_t)n];
 }
 
+// The rate kinds whose passes may fuse K steps: the kernel of such a pass, the PlanIn field
+// that holds its K, and the geometry of its k-step pass (mm_geom.hpp).
+struct RateKind {
+    Kernel kernel;
+    bool closed;  // steps: closed_k of a closed program, field_k of any other
+    int (*out_cols)(int k);
+    long long (*max_rows)(int k, long long pitch);
+    int steps(const PlanIn& in) const { return closed ? in.closed_k : in.field_k; }
+};
+const RateKind kRateKinds[] = {{kFieldK, false, passk_out_cols, fieldk_max_rows},
+                               {kClosedK, true, closedk_out_cols, closedk_max_rows}};
+
+// The kind whose passes the program fuses, K = steps(in) >= 2 steps each (the engine set
+// field_k / closed_k); nullptr: the program fuses no rate kind.
+const RateKind* fused_kind(const PlanIn& in) {
+    for (const RateKind& r : kRateKinds)
+        if (r.steps(in) >= 2 && in.closed == r.closed) return &r;
+    return nullptr;
+}
+
+const RateKind* rate_kind_of(Kernel kernel) {
+    for (const RateKind& r : kRateKinds)
+        if (r.kernel == kernel) return &r;
+    return nullptr;
+}
+
 // Edge-strip segment length / interior segment length of a k-step pass (MM_SEG_EDGE
 // overrides). mm_passk_kernel: the two edge strips run the general body, several times
 // slower per row than the branch-free one, and at K >= 8 it spills; their segments are cut
@@ -212,11 +238,10 @@ int wide_plan_first(const PlanIn& in, long long n, int kcap) {
 double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
     if (in.knobs.seg_edge > 0.0) return in.knobs.seg_edge;
     // mm_fieldk_kernel: the general body adds a short division per edge cell and keeps the
-    // levels interleaved; full-length edge segments until a measurement says otherwise
-    if (kernel == kFieldK) return 1.0;
+    // levels interleaved; full-length edge segments until a measurement says otherwise.
     // mm_closedk_kernel chooses its body from the data, row by row, in every strip alike:
     // full-length edge segments, not measured otherwise
-    if (kernel == kClosedK) return 1.0;
+    if (rate_kind_of(kernel)) return 1.0;
     if (kernel == kWide) return in.n_attr == 1 ? 1.0 : 0.5;
     if (k >= 10) return 0.1;
     if (k == 9) return 0.2;
@@ -224,9 +249,6 @@ double seg_edge_of(const PlanIn& in, Kernel kernel, int k) {
 }
 
 long long waves_for(long long nstrips, long long n, int th) { return n <= 0 ? 0 : nstrips * ceil_div(n, th); }
-
-bool fieldk_on(const PlanIn& in) { return in.field_k >= 2 && !in.closed; }
-bool closedk_on(const PlanIn& in) { return in.closed_k >= 2 && in.closed; }
 
 // MM_FIELD_STEPS unset: K = kFieldAutoSteps on slabs of at least kFieldAutoCells cells
 // (the table of tools/bench_field.py: the built K of the best time per step
@@ -271,7 +293,7 @@ int closed_k_for(const PlanIn& in, bool halo) {
     return k;
 }
 
-bool kstep_ok(const PlanIn& in) { return fieldk_on(in) || closedk_on(in) || passk_ok(in); }
+bool kstep_ok(const PlanIn& in) { return fused_kind(in) || passk_ok(in); }
 
 bool passk_ok(const PlanIn& in) {
     if (!in.knobs.passk || in.n_passes != 1 || in.field) return false;
@@ -294,10 +316,10 @@ namespace {
 
 // kernel_for but for the fused six-column pass
 KernelChoice kernel4_for(const PlanIn& in, int k) {
-    // a rate-field program in K-step passes: a pass of one step stays on mm_field_kernel
-    if (fieldk_on(in) && k >= 2) return {kFieldK, 2, ceil_div(in.W, passk_out_cols(k))};
-    // and a closed program's on mm_closed_kernel
-    if (closedk_on(in) && k >= 2) return {kClosedK, 2, ceil_div(in.W, closedk_out_cols(k))};
+    // a rate-field program in K-step passes: a pass of one step stays on mm_field_kernel, and
+    // a closed program's on mm_closed_kernel
+    const RateKind* r = fused_kind(in);
+    if (r && k >= 2) return {r->kernel, 2, ceil_div(in.W, r->out_cols(k))};
     if (!passk_ok(in)) return {kOneStep, 1, 0};  // one mm_pass_kernel launch per pass of the step
     if (use_wide(in, k)) return {kWide, wcols(in), ceil_div(in.W, wide_out_cols(k, wcols(in)))};
     return {kPassK, 2, ceil_div(in.W, passk_out_cols(k))};
@@ -314,8 +336,7 @@ KernelChoice kernel_for(const PlanIn& in, int k, bool red) {
 }
 
 int steps_per_launch(const PlanIn& in) {
-    if (fieldk_on(in)) return in.field_k;
-    if (closedk_on(in)) return in.closed_k;
+    if (const RateKind* r = fused_kind(in)) return r->steps(in);
     return passk_ok(in) ? passk_steps(in) : 1;
 }
 
@@ -326,9 +347,8 @@ int steps_per_launch(const PlanIn& in) {
 // the plan of least modelled time: 20 steps run as 10 + 10, a long run stays at K = 8
 // (1000 steps: 125 passes).
 int next_pass_len(const PlanIn& in, long long n) {
-    // a rate-field program: ceil(n / K) balanced passes (7 steps at K = 4: 4 + 3)
-    if (fieldk_on(in)) return (int)ceil_div(n, ceil_div(n, in.field_k));
-    if (closedk_on(in)) return (int)ceil_div(n, ceil_div(n, in.closed_k));  // the same
+    // a rate-field program, closed or not: ceil(n / K) balanced passes (7 steps at K = 4: 4 + 3)
+    if (const RateKind* r = fused_kind(in)) return (int)ceil_div(n, ceil_div(n, r->steps(in)));
     if (!passk_ok(in)) return 1;
     const Knobs& kn = in.knobs;
     const int kp = passk_steps(in);
@@ -385,10 +405,9 @@ long long seg_wave_count(long long n, long long ns, long long r, long long re) {
 // every workgroup, one per strip segment) fits seg_waves x the chip's resident slots (the
 // kernel's occupancy x CUs).
 Segments segments(const PlanIn& in, Kernel kernel, int k, int slots, long long n, long long ns) {
-    const long long maxr = std::max<long long>(
-        16, kernel == kFieldK    ? fieldk_max_rows(k, in.pitch)
-            : kernel == kClosedK ? closedk_max_rows(k, in.pitch)
-                                 : passk_max_rows(k, in.pitch));
+    const RateKind* rate = rate_kind_of(kernel);
+    const long long maxr =
+        std::max<long long>(16, rate ? rate->max_rows(k, in.pitch) : passk_max_rows(k, in.pitch));
     const double edge = seg_edge_of(in, kernel, k);
     const double units = ns < 3 ? (double)ns / edge : (double)(ns - 2) + 2.0 / edge;
     // even segment lengths: with an even first row (x_init and lo even, as every bench

@@ -9,170 +9,32 @@
 //     passes; a pass of one step stays on the one-step kernel.
 //   * closed_k_for is 0 with a halo, under MM_PASSK=0 and at a pitch whose closedk_max_rows is
 //     under 64; the engine's conditions (one attribute, exactly one closed diffusion) are
-//     restated by closed_k_of below; a knob value above the maximum clamps.
+//     mm::set_program's, asked through real flow lists; a knob value above the maximum clamps.
 //   * closedk_max_rows keeps every row the kernel addresses below 2^31 bytes.
 // Prints one line per failed check and exits 1, else "ok"; `plan_closedk_cli max` prints
 // kClosedMaxSteps.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "../mpi-model_amd/csrc/mm_plan.hpp"
+#include "plan_closed_cases.hpp"
 
 namespace {
-
-int g_failed = 0;
-
-void expect(bool ok, const char* what, int line) {
-    if (ok) return;
-    std::printf("line %d: %s\n", line, what);
-    g_failed = 1;
-}
-#define EXPECT(c) expect((c), #c, __LINE__)
-
-// Slab g of G of an H x W grid (mm_partition_rows), as the engine fills mm::PlanIn.
-mm::PlanIn slab(long long H, long long W, int G, int g, int n_attr, bool split) {
-    mm::PlanIn in;
-    in.H = H, in.W = W, in.nranks = G;
-    in.x_init = g * H / G;
-    in.h = (g + 1) * H / G - in.x_init;
-    in.min_rows = std::min(in.h, H / G);
-    in.pitch = (W + mm::kStripCols - 1) / mm::kStripCols * mm::kStripCols;
-    in.n_attr = n_attr;
-    in.split = split;
-    in.knobs.th = 8;
-    in.ncu = 256;
-    in.slots = [](mm::Kernel kernel, int k, bool) { return kernel == mm::kWide ? 2 : (k > 8 ? 4 : 8); };
-    return in;
-}
-
-// The programs the engine knew before the closed kind, as sync_program describes them.
-enum Program { kDiffuse, kC5, kField, kFieldAlone, kThreePasses };
-const char* const kProgramNames[] = {"diffuse", "c5", "field", "field_alone", "three_passes"};
-
-mm::PlanIn program(mm::PlanIn in, Program p, bool halo) {
-    in.n_passes = 1;
-    switch (p) {
-        case kDiffuse:
-            in.diffuse_mask = 1;
-            break;
-        case kC5:
-            in.diffuse_mask = 15, in.chains = true, in.ring = true;
-            break;
-        case kField:  // a field pass on an engine of several attributes: one step per pass
-            in.field = true;
-            break;
-        case kFieldAlone:  // exactly one field diffusion, one attribute: K-step passes
-            in.field = true;
-            in.field_k = mm::field_k_for(in, halo);
-            break;
-        case kThreePasses:
-            in.n_passes = 3;
-            break;
-    }
-    if (in.n_attr > 1 || in.field || in.chains) in.knobs.th = 8;
-    return in;
-}
-
-std::string launch_text(const mm::Launch& l) {
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "%lld-%lld,%lld-%lld s%d th%d/%d x%d n%d w%lld/%lld b%lld", l.lo, l.hi,
-                  l.lo2, l.hi2, l.seg, l.th, l.th_edge, l.xcd_remap, l.nstrips, l.waves_a,
-                  l.waves_total, l.partial_base);
-    return buf;
-}
-
-// Everything the engine asks the planner about a program, as one line.
-std::string plan_text(const mm::PlanIn& in) {
-    std::string s;
-    char buf[256];
-    const mm::SlabPlan sp = mm::slab_plan(in);
-    std::snprintf(buf, sizeof buf, "k%d spl%d rpw%d w%lld sw%d ok%d v%d need%lld |", (int)sp.kernel,
-                  sp.steps_per_launch, sp.rows_per_wave, sp.waves_per_pass, sp.seg_waves_per_cu,
-                  (int)mm::kstep_ok(in), mm::kernel_variant(in), mm::partials_need(in));
-    s += buf;
-    for (long long n : {1LL, 7LL, 20LL, 64LL}) {
-        s += " [";
-        for (int l : mm::pass_lengths(in, n)) s += std::to_string(l) + " ";
-        s += "]";
-    }
-    std::snprintf(buf, sizeof buf, " g%lld/%lld/%lld |", mm::graph_per(in, 20, 0), mm::graph_per(in, 64, 1),
-                  mm::graph_per(in, 7, 3, true));
-    s += buf;
-    for (int k : {1, sp.steps_per_launch})
-        for (int red = 0; red < 2; ++red) {
-            const mm::PassLaunches p = mm::pass_launches(in, k, red != 0);
-            std::snprintf(buf, sizeof buf, " {k%d c%d st%lld d%d sp%d t%lld ", (int)p.kern.kernel,
-                          p.kern.cols, p.kern.strips, p.depth, (int)p.split, p.total);
-            s += buf + launch_text(p.interior) + " ; " + launch_text(p.border) + "}";
-        }
-    return s;
-}
-
-struct Case {
-    long long H, W;
-    int G, g, n_attr;
-    bool split;
-    Program p;
-    int field_steps, field_halo;
-};
-
-const Case kCases[] = {
-    {130, 97, 1, 0, 1, false, kDiffuse, 0, 1},      {2048, 2048, 1, 0, 1, false, kDiffuse, 0, 1},
-    {8192, 8192, 1, 0, 1, false, kDiffuse, 0, 1},   {32768, 32768, 1, 0, 1, false, kDiffuse, 4, 4},
-    {32768, 32768, 8, 3, 1, true, kDiffuse, 0, 1},  {4096, 4096, 1, 0, 4, false, kC5, 0, 1},
-    {67, 300, 3, 1, 4, true, kC5, 4, 4},            {130, 257, 1, 0, 3, false, kField, 4, 4},
-    {27, 257, 3, 1, 2, true, kField, 0, 2},         {130, 257, 1, 0, 1, false, kFieldAlone, 0, 1},
-    {2048, 2048, 1, 0, 1, false, kFieldAlone, 0, 1}, {8192, 8192, 1, 0, 1, false, kFieldAlone, 3, 1},
-    {8192, 8192, 1, 0, 1, true, kFieldAlone, 0, 4}, {8192, 8192, 1, 0, 1, true, kFieldAlone, 4, 1},
-    {27, 257, 3, 1, 1, true, kFieldAlone, 4, 4},    {4096, 2048, 2, 1, 1, true, kFieldAlone, 0, 4},
-    {130, 97, 1, 0, 3, false, kThreePasses, 4, 4},  {8192, 8192, 2, 0, 2, true, kThreePasses, 0, 1},
-};
-
-std::string case_text(const Case& c) {
-    mm::PlanIn in = slab(c.H, c.W, c.G, c.g, c.n_attr, c.split);
-    in.knobs.field_steps = c.field_steps;
-    in.knobs.field_halo = c.field_halo;
-    in = program(in, c.p, c.split);
-    char buf[128];
-    std::snprintf(buf, sizeof buf, "%s %lldx%lld %d/%d na%d fs%d fh%d: ", kProgramNames[c.p], c.H, c.W, c.g,
-                  c.G, c.n_attr, c.field_steps, c.field_halo);
-    return buf + plan_text(in);
-}
-
-// `plan_closed_cli table` of the planner before the closed kind
-const char* const kTable[] = {
-#include "plan_closed_table.inc"
-};
-
-
-// What mm_engine.hip's sync_program computes: closed_k_for only for a one-attribute engine
-// whose flow list is exactly one closed diffusion.
-int closed_k_of(const mm::PlanIn& in, int n_closed, int n_other, bool halo) {
-    return in.n_attr == 1 && n_closed == 1 && n_other == 0 ? mm::closed_k_for(in, halo) : 0;
-}
-
-mm::Knobs knobs_of(const std::map<std::string, std::string>& env) {
-    return mm::read_knobs([&](const char* name) -> const char* {
-        const auto it = env.find(name);
-        return it == env.end() ? nullptr : it->second.c_str();
-    });
-}
 
 // A one-attribute slab without a halo whose program is one closed diffusion.
 mm::PlanIn closed_alone(long long H, long long W, const std::map<std::string, std::string>& env) {
     mm::PlanIn in = slab(H, W, 1, 0, 1, false);
     in.knobs = knobs_of(env);
-    in.knobs.th = 8;
-    in.n_passes = 1;
-    in.field = in.closed = true;
-    in.field_k = mm::field_k_for(in, false);
-    in.closed_k = closed_k_of(in, 1, 0, false);
+    in = with_flows(in, {C(0)}, false);
+    EXPECT(in.n_passes == 1 && in.field && in.closed && in.knobs.th == 8);
     return in;
+}
+
+// closed_k of slab `in` (its knobs set) under the program of `flows`.
+int closed_k_with(const mm::PlanIn& in, const std::vector<mm::Flow>& flows, bool halo) {
+    return with_flows(in, flows, halo).closed_k;
 }
 
 void check_off(const mm::PlanIn& in) {
@@ -238,27 +100,10 @@ int main(int argc, char** argv) {
         return 0;
     }
     // the knob unset: the table of the planner before the closed kind, line for line
-    const size_t n = sizeof kCases / sizeof kCases[0];
-    EXPECT(sizeof kTable / sizeof kTable[0] == n);
-    for (size_t i = 0; i < n && i < sizeof kTable / sizeof kTable[0]; ++i)
-        if (case_text(kCases[i]) != kTable[i]) {
-            std::printf("plan changed:\n  was %s\n  is  %s\n", kTable[i], case_text(kCases[i]).c_str());
-            g_failed = 1;
-        }
+    check_table();
     // ... and with the knob set, which no program of the table reads
-    for (size_t i = 0; i < n && i < sizeof kTable / sizeof kTable[0]; ++i) {
-        const Case& c = kCases[i];
-        mm::PlanIn in = slab(c.H, c.W, c.G, c.g, c.n_attr, c.split);
-        in.knobs.field_steps = c.field_steps;
-        in.knobs.field_halo = c.field_halo;
-        in.knobs.closed_steps = mm::kClosedMaxSteps;
-        in = program(in, c.p, c.split);
-        EXPECT(closed_k_of(in, 0, 1, c.split) == 0);
-        char buf[128];
-        std::snprintf(buf, sizeof buf, "%s %lldx%lld %d/%d na%d fs%d fh%d: ", kProgramNames[c.p], c.H, c.W, c.g,
-                      c.G, c.n_attr, c.field_steps, c.field_halo);
-        EXPECT(buf + plan_text(in) == kTable[i]);
-    }
+    check_table(mm::kClosedMaxSteps);
+    for (const Case& c : kCases) EXPECT(case_in(c, mm::kClosedMaxSteps).closed_k == 0);
     // defaults mean "off"
     EXPECT(mm::Knobs().closed_steps == 0 && mm::PlanIn().closed_k == 0);
     EXPECT(mm::kClosedMaxSteps >= 2 && (int)mm::kClosedK == 5);
@@ -297,11 +142,12 @@ int main(int argc, char** argv) {
         mm::PlanIn in = closed_alone(130, 257, on);
         EXPECT(mm::closed_k_for(in, false) == 3);
         EXPECT(mm::closed_k_for(in, true) == 0);   // a halo: a chain, any halo mode, MM_SELF_HALO
-        EXPECT(closed_k_of(in, 1, 1, false) == 0);  // [TRANSFER, CLOSED]
-        EXPECT(closed_k_of(in, 2, 0, false) == 0);
+        EXPECT(closed_k_with(in, {C(0)}, false) == 3);
+        EXPECT(closed_k_with(in, {T(0, -1), C(0)}, false) == 0);
+        EXPECT(closed_k_with(in, {C(0), C(0)}, false) == 0);
         mm::PlanIn two = in;
         two.n_attr = 2;
-        EXPECT(closed_k_of(two, 1, 0, false) == 0);  // two attributes
+        EXPECT(closed_k_with(two, {C(0)}, false) == 0);  // two attributes
         mm::PlanIn open = in;
         open.closed = false;  // a field program is not a closed one
         EXPECT(mm::closed_k_for(open, false) == 0);
@@ -312,9 +158,8 @@ int main(int argc, char** argv) {
         for (int g = 0; g < 3; ++g) {
             mm::PlanIn c = slab(27, 257, 3, g, 1, true);
             c.knobs = knobs_of({{"MM_CLOSED_STEPS", "4"}, {"MM_FIELD_HALO", "2"}});
-            c.knobs.th = 8, c.n_passes = 1, c.field = c.closed = true;
-            c.closed_k = closed_k_of(c, 1, 0, true);
-            c.field_k = mm::field_k_for(c, true);
+            c = with_flows(c, {C(0)}, true);
+            EXPECT(c.closed && mm::field_k_for(c, true) == 0);
             check_off(c);
         }
         // a pitch whose closedk_max_rows is under 64

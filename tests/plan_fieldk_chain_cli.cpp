@@ -3,49 +3,23 @@
 // plan of mm_fieldk_kernel), for tests/test_fieldk_chain_cpu.py. Built with plain g++ (no
 // ROCm headers). Prints one line per failed check and exits 1, else "ok <kFieldMaxSteps>".
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../mpi-model_amd/csrc/mm_plan.hpp"
+#include "plan_test.hpp"
 
 namespace {
 
-int g_failed = 0;
-
-void expect(bool ok, const char* what, int line) {
-    if (ok) return;
-    std::printf("line %d: %s\n", line, what);
-    g_failed = 1;
-}
-#define EXPECT(c) expect((c), #c, __LINE__)
-
-// Slab g of G of an H x W grid (mm_partition_rows), one attribute, one rate-field pass, as
-// the engine fills mm::PlanIn for a host-transport chain.
+// Slab g of G of an H x W grid, one attribute, the program one rate-field diffusion, 8 slots
+// per CU whatever the kernel. field_k is left to the checks, which set it themselves.
 mm::PlanIn slab(long long H, long long W, int G, int g) {
-    mm::PlanIn in;
-    in.H = H, in.W = W, in.nranks = G;
-    in.x_init = g * H / G;
-    in.h = (g + 1) * H / G - in.x_init;
-    in.min_rows = std::min(in.h, H / G);
-    in.pitch = (W + mm::kStripCols - 1) / mm::kStripCols * mm::kStripCols;
-    in.n_attr = 1, in.n_passes = 1, in.diffuse_mask = 0;
-    in.field = true;
-    in.split = G > 1;
-    in.knobs.th = 8;
-    in.ncu = 256;
+    mm::PlanIn in = with_flows(slab(H, W, G, g, 1, G > 1), {F(0)}, G > 1);
+    EXPECT(in.field && in.n_passes == 1 && in.diffuse_mask == 0 && in.knobs.th == 8);
+    in.field_k = 0;
     in.slots = [](mm::Kernel, int, bool) { return 8; };
     return in;
 }
-
-mm::Knobs knobs_of(const char* name, const char* value) {
-    return mm::read_knobs([&](const char* n) -> const char* {
-        return std::strcmp(n, name) == 0 ? value : nullptr;
-    });
-}
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
 // The launches of every pass length of a chain slab whose field_k is K.
 void check_split(const mm::PlanIn& base, int K) {

@@ -3,75 +3,22 @@
 // tests/test_fieldk_cpu.py. Built with plain g++ (no ROCm headers). Prints one line per
 // failed check and exits 1, else "ok <kFieldMaxSteps>".
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "../mpi-model_amd/csrc/mm_plan.hpp"
+#include "plan_test.hpp"
 
 namespace {
 
-int g_failed = 0;
-
-void expect(bool ok, const char* what, int line) {
-    if (ok) return;
-    std::printf("line %d: %s\n", line, what);
-    g_failed = 1;
-}
-#define EXPECT(c) expect((c), #c, __LINE__)
-
-// Slab g of G of an H x W grid (mm_partition_rows), one attribute, one rate-field pass.
+// Slab g of G of an H x W grid, one attribute, the program one rate-field diffusion, 8 slots
+// per CU whatever the kernel. field_k is left to the checks, which set it themselves.
 mm::PlanIn slab(long long H, long long W, int G, int g) {
-    mm::PlanIn in;
-    in.H = H, in.W = W, in.nranks = G;
-    in.x_init = g * H / G;
-    in.h = (g + 1) * H / G - in.x_init;
-    in.min_rows = std::min(in.h, H / G);
-    in.pitch = (W + mm::kStripCols - 1) / mm::kStripCols * mm::kStripCols;
-    in.n_attr = 1, in.n_passes = 1, in.diffuse_mask = 0;
-    in.field = true;
-    in.split = G > 1;
-    in.knobs.th = 8;  // what the engine sets for a program with a rate-field pass
-    in.ncu = 256;
+    mm::PlanIn in = with_flows(slab(H, W, G, g, 1, G > 1), {F(0)}, G > 1);
+    EXPECT(in.field && in.n_passes == 1 && in.diffuse_mask == 0 && in.knobs.th == 8);
+    in.field_k = 0;
     in.slots = [](mm::Kernel, int, bool) { return 8; };
     return in;
-}
-
-mm::Knobs knobs_of(const char* name, const char* value) {
-    return mm::read_knobs([&](const char* n) -> const char* {
-        return std::strcmp(n, name) == 0 ? value : nullptr;
-    });
-}
-
-long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
-
-// field_k = 0: the one-step answers of today, whatever the rest of the input says
-void check_off(const mm::PlanIn& on) {
-    EXPECT(on.field_k == 0);
-    EXPECT(!mm::passk_ok(on) && !mm::kstep_ok(on));
-    EXPECT(mm::steps_per_launch(on) == 1);
-    EXPECT(mm::pass_lengths(on, 7) == std::vector<int>(7, 1));
-    EXPECT(mm::next_pass_len(on, 20) == 1);
-    EXPECT(mm::kernel_for(on, 1).kernel == mm::kOneStep);
-    EXPECT(mm::kernel_for(on, 4).kernel == mm::kOneStep);
-    EXPECT(mm::slab_plan(on).kernel == mm::kOneStep);
-    EXPECT(mm::slab_plan(on).steps_per_launch == 1);
-    for (int red = 0; red < 2; ++red) {
-        const mm::PassLaunches p = mm::pass_launches(on, 1, red);
-        const long long h = on.h, ns = on.pitch / mm::kStripCols;
-        EXPECT(p.kern.kernel == mm::kOneStep && p.depth == 1);
-        EXPECT(p.interior.nstrips == ns && p.interior.th == 8 && p.interior.seg == 0);
-        if (on.split && h >= 3) {
-            EXPECT(p.split && p.interior.lo == 1 && p.interior.hi == h - 1);
-            EXPECT(p.border.th == 1 && p.border.waves_total == 2 * ns);
-        } else {
-            EXPECT(!p.split && p.interior.lo == 0 && p.interior.hi == h);
-        }
-        EXPECT(p.interior.waves_total == ns * ((p.interior.hi - p.interior.lo + 7) / 8));
-        EXPECT(p.total * mm::kMaxAttr <= mm::partials_need(on));
-    }
-    EXPECT(mm::graph_per(on, 64, 0) > 0 && mm::graph_per(on, 64, 0) % 2 == 0);
 }
 
 void check_on(const mm::PlanIn& base, int K) {
@@ -150,9 +97,9 @@ int main() {
                                    {32768, 32768, 8, 3}};
     for (const auto& s : shapes) {
         mm::PlanIn on = slab(s[0], s[1], (int)s[2], (int)s[3]);
-        check_off(on);
+        check_one_step(on);
         on.knobs.field_steps = 4;  // the knob alone changes no plan: the engine sets field_k
-        check_off(on);
+        check_one_step(on);
     }
 
     // what the engine asks before it sets field_k

@@ -7,15 +7,14 @@ way tests/test_plan.py builds its program), and the constant in header and bindi
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import closed_model as cm
+from plan_build import REPO, SANITIZE, build, run
 from value_classes import assert_same_bits
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "mpimodel.h")
 SHAPES = [(1, 1), (1, 9), (2, 2), (3, 3), (13, 6), (27, 257), (130, 97)]
 # the embedded rectangles: (rows, columns) at (row, column) of 27 x 257 -- a corner of the
@@ -131,16 +130,9 @@ def test_zero_of_either_sign_is_a_wall():
 
 
 # ---- the planner -------------------------------------------------------------
-PLAN_SRCS = [os.path.join(REPO, "tests", "plan_closed_cli.cpp"),
-             os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
-
-
 def build_and_run(exe, *flags):
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *PLAN_SRCS,
-                        "-o", exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout[-3000:] + r.stderr[-3000:]
+    out = run(build(exe, "plan_closed_cli.cpp", *flags))
+    assert out.strip() == "ok", out[-3000:]
 
 
 def test_planner_keeps_closed_programs_at_one_step(tmp_path):
@@ -150,8 +142,7 @@ def test_planner_keeps_closed_programs_at_one_step(tmp_path):
 
 
 def test_planner_under_sanitizers(tmp_path):
-    build_and_run(str(tmp_path / "plan_closed_cli_san"), "-g", "-fsanitize=address,undefined",
-                  "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")
+    build_and_run(str(tmp_path / "plan_closed_cli_san"), *SANITIZE)
 
 
 # ---- header and binding ---------------------------------------------------------

@@ -5,18 +5,15 @@ numpy with tests/closed_model.py; the geometry of mm_geom.hpp against that cone;
 once more as a stand-alone program under the sanitizers); the constant in header and binding."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import closed_model as cm
 from closedk_geom import geom
+from plan_build import REPO, SANITIZE, build, run
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "mpimodel.h")
-PLAN_SRCS = [os.path.join(REPO, "tests", "plan_closedk_cli.cpp"),
-             os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
 N, C = 41, 20  # the cone's grid and its centre
 
 
@@ -100,12 +97,9 @@ def test_strip_halo_covers_the_cone():
 
 # ---- the planner -------------------------------------------------------------
 def build_and_run(exe, *flags):
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *PLAN_SRCS,
-                        "-o", exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout[-3000:] + r.stderr[-3000:]
-    return int(subprocess.run([exe, "max"], capture_output=True, text=True, check=True).stdout)
+    out = run(build(exe, "plan_closedk_cli.cpp", *flags))
+    assert out.strip() == "ok", out[-3000:]
+    return int(run(exe, "max"))
 
 
 def test_planner(tmp_path, mm):
@@ -113,8 +107,7 @@ def test_planner(tmp_path, mm):
 
 
 def test_planner_under_sanitizers(tmp_path):
-    build_and_run(str(tmp_path / "plan_closedk_cli_san"), "-g", "-fsanitize=address,undefined",
-                  "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")
+    build_and_run(str(tmp_path / "plan_closedk_cli_san"), *SANITIZE)
 
 
 # ---- header and binding ---------------------------------------------------------

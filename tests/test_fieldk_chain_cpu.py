@@ -5,21 +5,16 @@ blocks, partials), the balanced pass lengths and the header's text
 the way tests/test_fieldk_cpu.py builds its program, and once more under ASan + UBSan as a
 stand-alone program)."""
 import os
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(REPO, "tests", "plan_fieldk_chain_cli.cpp"),
-        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+from plan_build import REPO, SANITIZE, build, run
+
 HEADER = os.path.join(REPO, "include", "mpimodel.h")
 
 
 def build_and_run(exe, *flags):
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *SRCS,
-                        "-o", exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    r = subprocess.run([exe, HEADER], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-3000:] + r.stderr[-3000:]
-    return int(r.stdout.split()[1])  # the planner's kFieldMaxSteps
+    out = run(build(exe, "plan_fieldk_chain_cli.cpp", *flags), HEADER)
+    assert out.startswith("ok "), out[-3000:]
+    return int(out.split()[1])  # the planner's kFieldMaxSteps
 
 
 def test_planner_splits_field_passes(tmp_path, mm):
@@ -27,10 +22,7 @@ def test_planner_splits_field_passes(tmp_path, mm):
 
 
 def test_planner_under_sanitizers(tmp_path, mm):
-    k = build_and_run(str(tmp_path / "plan_fieldk_chain_cli_san"), "-g",
-                      "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                      "-static-libasan", "-static-libubsan")
-    assert k == mm.FIELD_MAX_STEPS
+    assert build_and_run(str(tmp_path / "plan_fieldk_chain_cli_san"), *SANITIZE) == mm.FIELD_MAX_STEPS
 
 
 def test_header_names_the_knob():

@@ -5,20 +5,14 @@ plain g++ the way tests/test_ratefield_cpu.py builds its program, and once more 
 UBSan as a stand-alone program the way tests/test_plan.py builds its own)."""
 import os
 import re
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(REPO, "tests", "plan_fieldk_cli.cpp"),
-        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+from plan_build import REPO, SANITIZE, build, run
 
 
 def build_and_run(exe, *flags):
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *SRCS,
-                        "-o", exe], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-3000:] + r.stderr[-3000:]
-    return int(r.stdout.split()[1])  # the planner's kFieldMaxSteps
+    out = run(build(exe, "plan_fieldk_cli.cpp", *flags))
+    assert out.startswith("ok "), out[-3000:]
+    return int(out.split()[1])  # the planner's kFieldMaxSteps
 
 
 def header_max_steps():
@@ -38,6 +32,4 @@ def test_planner_fuses_field_passes(tmp_path):
 
 
 def test_planner_under_sanitizers(tmp_path):
-    k = build_and_run(str(tmp_path / "plan_fieldk_cli_san"), "-g", "-fsanitize=address,undefined",
-                      "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")
-    assert k == header_max_steps()
+    assert build_and_run(str(tmp_path / "plan_fieldk_cli_san"), *SANITIZE) == header_max_steps()

@@ -6,14 +6,12 @@ of a chain, segment plans that fit their slots, pass launches that cover the sla
 and stay inside the partials buffer."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(REPO, "tests", "plan_cli.cpp"),
-        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+from plan_build import REPO, SANITIZE, build, run
+
 CHAINS = [(64, 300, 2), (37, 130, 3), (27, 257, 3), (100, 488, 3), (41, 200, 8),
           (24, 257, 8), (16, 130, 8), (9, 124, 8), (300, 700, 2)]  # test_gpu_halo.py
 C5_CHAINS = [(67, 300, 3), (40, 130, 8)]
@@ -21,16 +19,9 @@ PASSK_K = tuple(range(1, 11))
 WIDE_K = (4, 8, 12, 16, 20)
 
 
-def compile_cli(exe, *flags):
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *flags, *SRCS, "-o", exe],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def cli(tmp_path_factory):
-    return compile_cli(str(tmp_path_factory.mktemp("plan") / "plan_cli"))
+    return build(str(tmp_path_factory.mktemp("plan") / "plan_cli"), "plan_cli.cpp")
 
 
 @pytest.fixture(scope="module")
@@ -58,9 +49,8 @@ def table():
 
 def ask(exe, lines):
     """Run the commands; one list of ints per answered query."""
-    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    return [[int(x) for x in ln.split()] for ln in p.stdout.split("\n")[:-1]]
+    out = run(exe, input="\n".join(lines) + "\n")
+    return [[int(x) for x in ln.split()] for ln in out.split("\n")[:-1]]
 
 
 def slab_lines(H, W, G=1, g=0, program="diffuse", env=None, ncu=256, swpc=8, x0=None, h=None):
@@ -110,8 +100,7 @@ def test_recorded_plans_replay_on_the_cpu(cli, table):
 def test_recorded_plans_under_sanitizers(tmp_path, table):
     """The same program under ASan + UBSan (runtimes linked statically into the stand-alone
     program), once over the whole table and over a sweep of launches."""
-    exe = compile_cli(str(tmp_path / "plan_cli_san"), "-g", "-fsanitize=address,undefined",
-                      "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan")
+    exe = build(str(tmp_path / "plan_cli_san"), "plan_cli.cpp", *SANITIZE)
     lines = table_script(table) + ["graph 1000 3 0", "graph 48 1 1"]
     for h in (1, 26, 27, 41, 120):
         lines += slab_lines(2 * h, 300, 2, 0, env={"MM_WIDE": 1})
@@ -191,9 +180,7 @@ def test_segment_plans(cli, na, kernel, ks, seg_waves):
     lines = slab_lines(600, 293 * 100, program="c5" if na == 4 else "diffuse", env=env, ncu=ncu)
     keys = [(k, s, ns) for k in ks for s in range(1, 17) for ns in strips]
     lines += [f"seg {kernel} {k} {s} 1 600 {ns}" for k, s, ns in keys]
-    p = subprocess.run([cli], input="\n".join(lines) + "\n", capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
-    out = np.array(p.stdout.split(), dtype=np.int64).reshape(len(keys), 600, 4)
+    out = np.array(run(cli, input="\n".join(lines) + "\n").split(), dtype=np.int64).reshape(len(keys), 600, 4)
     n = np.arange(1, 601)[None, :]
     slots = np.array([s for _, s, _ in keys])[:, None]
     ns = np.array([x for _, _, x in keys])[:, None]

@@ -4,14 +4,10 @@ every column once and leaves the grid's last column to the frame whatever W % 6 
 interior segment reads interior rows and columns only (the FAST body's condition), segment
 lengths are even, the blocks add up, and every shape the rule leaves out plans exactly as
 without the fused instance."""
-import os
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(REPO, "tests", "plan6_cli.cpp"),
-        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+import plan_build
+
 K = 20
 O4, O6, HALO6 = 216, 336, 24  # output columns of a 4- / 6-column strip, a 6-column strip's halo
 FIELDS = ("lo hi lo2 hi2 seg th th_edge xcd nstrips waves_a waves_total partial_base "
@@ -22,17 +18,11 @@ WIDTHS = (32768, 16384, 770, 768, 1000)
 
 @pytest.fixture(scope="module")
 def cli(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("plan6") / "plan6_cli")
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *SRCS, "-o", exe],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    return exe
+    return plan_build.build(str(tmp_path_factory.mktemp("plan6") / "plan6_cli"), "plan6_cli.cpp")
 
 
 def run(exe, lines):
-    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    return p.stdout
+    return plan_build.run(exe, input="\n".join(lines) + "\n")
 
 
 def slab(H, W, env=None, s6=2, G=1, g=0, split=0, n_attr=1, ncu=256):

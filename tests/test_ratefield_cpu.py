@@ -4,11 +4,8 @@ header and the binding, and the planner's treatment of a program with a rate-fie
 way tests/test_plan.py builds its program)."""
 import os
 import re
-import subprocess
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = [os.path.join(REPO, "tests", "plan_field_cli.cpp"),
-        os.path.join(REPO, "mpi-model_amd", "csrc", "mm_plan.cpp")]
+from plan_build import REPO, build, run
 
 
 def test_flow_kind_in_header_is_the_bindings(mm):
@@ -23,9 +20,5 @@ def test_flow_kind_in_header_is_the_bindings(mm):
 
 
 def test_planner_runs_field_programs_one_step_per_pass(tmp_path):
-    exe = str(tmp_path / "plan_field_cli")
-    p = subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", *SRCS, "-o", exe],
-                       capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout[-3000:] + r.stderr[-1000:]
+    out = run(build(str(tmp_path / "plan_field_cli"), "plan_field_cli.cpp"))
+    assert out.strip() == "ok", out[-3000:]
