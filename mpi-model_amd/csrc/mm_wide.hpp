@@ -85,6 +85,10 @@ namespace {
 // registers per level fewer, the scheduler interleaves consecutive iterations instead).
 constexpr int kSkew = MM_WIDE_ASC ? 2 : 3;
 
+#ifndef MM_WIDE6_MASK
+#define MM_WIDE6_MASK 1  // 0: fast_segment keeps the halo lanes no level of the wave needs in EXEC
+#endif
+
 enum { kBodyFast = 0, kBodyEdge = 1, kBodyGen = 2 };
 
 // What every level of a wave needs besides its windows.
@@ -1002,6 +1006,20 @@ __device__ __forceinline__ void fast_segment(const PassArgs& A, dv2* lds, int p,
     const int need = (P - 1) * G::D + G::S0 + (x.rB - x.rA);
     const int iend = (need + G::B - 1) / G::B * G::B;
     constexpr bool kMidPar = ((KW | G::D) & 1) != 0;
+#if MM_WIDE6_MASK
+    // Halo lanes this wave does not need. The strip's output is level K's columns from C * LH
+    // on, which read level j's output from column C * LH - (K - j) on and so level j's input
+    // from one column before that, mirrored on the right. Wave p's first level is p * KW + 1:
+    // a lane whose C columns all lie left of column C * LH - K + p * KW (or right of its
+    // mirror) holds nothing this wave's levels or a later wave's read -- 0 / 1 / 2 / 3 lanes
+    // a side for waves 0..3 at K = 20, C = 6, 4.7 % of the lane operations. They leave EXEC
+    // here, once per wave (less switching power, no cycle saved: DESIGN.md section 5.1); the
+    // wave runs the same instructions and reaches every barrier. DPP reads 0 from a lane out
+    // of EXEC (bound_ctrl), as it does past the wave's ends; the ring rows such a lane no
+    // longer writes are read only by the same lane of the next wave, out of its EXEC too.
+    const int dead = C * LH - K + p * KW;
+    if (C * lane + C - 1 < dead || C * lane > 64 * C - 1 - dead) return;
+#endif
     if (p == 0)
         wave_run_fast<C, KW, P, U, B, NT, kRoleFirst, 0>(x, iend);
     else if (p == P - 1)

@@ -2,8 +2,8 @@
 
 usage: asm_loops.py FILE.s KERNEL_SUBSTRING
 A loop is a backward branch to a label; its body is every line between the label and the
-branch. Counts: VALU (v_*), fp64 VALU (v_*_f64), DPP moves, buffer loads/stores, scratch,
-s_waitcnt, s_nop. Used to check what the steady-state loop of the K-step kernel issues.
+branch. Counts: VALU (v_*), fp64 VALU (v_*_f64), DPP moves, ds_bpermute and other DS instructions,
+buffer loads/stores, scratch, s_waitcnt, s_nop. Used to check what the steady-state loop of the K-step kernel issues.
 """
 import re
 import sys
@@ -36,6 +36,10 @@ def mix(body):
                 c["dpp"] += 1
             if op.startswith("v_mov") or op.startswith("v_accvgpr"):
                 c["mov"] += 1
+        elif op.startswith("ds_bpermute"):
+            c["bpermute"] += 1
+        elif op.startswith("ds_"):
+            c["ds"] += 1
         elif op.startswith("buffer_load"):
             c["bload"] += 1
         elif op.startswith("buffer_store"):
