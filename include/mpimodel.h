@@ -107,16 +107,22 @@ enum mm_flow_kind {
      * and MM_FIELD_HALO have no effect on a program that holds one. Such a program runs one
      * step per pass, halo depth 1 (mm_info.kernel and mm_pass_kernel report 0) -- except, with
      * MM_CLOSED_STEPS=K (2..MM_CLOSED_MAX_STEPS) in the creation environment, a program that
-     * is exactly one closed diffusion on a one-attribute engine whose slab has no halo
-     * (nranks == 1, MM_HALO_NONE): its passes fuse up to K steps on mm_closedk_kernel
-     * (mm_info.kernel 5), bit for bit the same result; a run of n steps is ceil(n / K)
-     * balanced passes, a pass of one step runs mm_closed_kernel. One step reads v of
-     * rows x-1..x+1 but f of rows x-2..x+2 (the share of row x+1 needs the count of row
-     * x+1, which needs the openness of row x+2). So on a slab with a halo (a chain, any halo
-     * mode, MM_SELF_HALO) the engine must have been created with MM_FIELD_HALO=2 or more,
-     * and two ghost rows of the field (rows -2..h+1, clipped to the grid) must have been
-     * uploaded on every side with a neighbour: mm_run / mm_prepare return MM_ERR_STATE
-     * otherwise, before anything is enqueued. */
+     * is exactly one closed diffusion on a one-attribute engine: its passes fuse up to K
+     * steps on mm_closedk_kernel (mm_info.kernel 5), bit for bit the same result; a run of n
+     * steps is ceil(n / K) balanced passes, a pass of one step runs mm_closed_kernel. On a
+     * slab with a halo (below) K is min(MM_CLOSED_STEPS, MM_CLOSED_HALO - 1, the chain's
+     * thinnest slab), one step per pass under 2 and with MM_CLOSED_HALO unset: a K-step pass
+     * reads K ghost rows of v, which the engine exchanges (mm_info.halo_depth = K), and K + 1
+     * ghost rows of f, which it never does -- the slab uploads rows -(K+1)..h+K of its field
+     * (clipped to the grid), and mm_run / mm_prepare return MM_ERR_STATE before anything is
+     * enqueued while a side with a neighbour holds fewer. MM_CLOSED_HALO=5 reaches K = 4. One
+     * step reads v of rows x-1..x+1 but f of rows x-2..x+2 (the share of row x+1 needs the
+     * count of row x+1, which needs the openness of row x+2). So on a slab with a halo (a
+     * chain, any halo mode, MM_SELF_HALO) the engine must have been created with
+     * MM_FIELD_HALO=2 or more (or MM_CLOSED_HALO=2 or more), and two ghost rows of the field
+     * (rows -2..h+1, clipped to the grid) must have been uploaded on every side with a
+     * neighbour: mm_run / mm_prepare return MM_ERR_STATE otherwise, before anything is
+     * enqueued. */
     MM_FLOW_DIFFUSE_CLOSED = 4
 };
 
@@ -283,10 +289,15 @@ int mm_device_synchronize(int device);
  * rate-field passes of a slab with a halo fuse up to d steps; unset, 0, 1 or anything else:
  * 1, one step per pass there),
  * MM_CLOSED_STEPS (steps per pass of a program that is one closed rate-field diffusion of a
- * one-attribute engine on a slab without a halo: 2..MM_CLOSED_MAX_STEPS that K on
- * mm_closedk_kernel, a larger value MM_CLOSED_MAX_STEPS; 0, 1 or unset one step per pass --
- * there is no default by slab size; with a halo, several attributes, further flows or
- * MM_PASSK=0 it has no effect),
+ * one-attribute engine: 2..MM_CLOSED_MAX_STEPS that K on mm_closedk_kernel, a larger value
+ * MM_CLOSED_MAX_STEPS; 0, 1 or unset one step per pass -- there is no default by slab size;
+ * with several attributes, further flows or MM_PASSK=0 it has no effect, and on a slab with a
+ * halo K is also bounded by MM_CLOSED_HALO - 1 and by the chain's thinnest slab),
+ * MM_CLOSED_HALO (d = 2..MM_CLOSED_MAX_STEPS + 1: the caller's promise that on every side
+ * where this slab has a neighbour the rate field of a closed diffusion gets d valid ghost rows,
+ * which lets the closed passes of a slab with a halo fuse up to d - 1 steps; 2 or more also
+ * satisfies the one-step closed pass, as MM_FIELD_HALO=2 does, while MM_FIELD_HALO lets no
+ * closed pass fuse; unset, 0, 1, 6 or anything else: unset, one step per pass there),
  * MM_WIDE_COLS (6: every K = 20 pass whose shape allows it -- one attribute, no halo, no step
  * sums in the pass, at least 577 columns -- runs as the fused pass of mm_wide6_kernel, the
  * grid's frame at 4 columns per lane and its interior at 6, whatever the slab's size; 4:
@@ -298,8 +309,8 @@ int mm_device_synchronize(int device);
  * exchange border rows with itself (ghost rows outside the grid: exercises the RCCL
  * path, result unchanged).
  * An RCCL chain runs in lockstep: every rank must call mm_prepare / mm_run with the same
- * step counts and reduce_every, with the same MM_GRAPH* settings, the same MM_FIELD_HALO
- * (like every plan input it is rank-invariant) and the same timing mode
+ * step counts and reduce_every, with the same MM_GRAPH* settings, the same MM_FIELD_HALO,
+ * MM_CLOSED_HALO and MM_CLOSED_STEPS (like every plan input they are rank-invariant) and the same timing mode
  * (mm_set_timing), so that all ranks run the same K-row exchanges and capture the same
  * graphs at the same call (the first capture of each graph agrees on success with one
  * all-reduce, after draining this engine's streams). */

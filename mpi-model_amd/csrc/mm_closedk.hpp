@@ -10,8 +10,10 @@
 // row), the K levels skewed (at iteration i level j consumes input row i - 2(j-1) of the
 // segment), a per-level window of s, s, d, the pend hand-off between levels, one rows_rsrc
 // descriptor per wave and buffer, the register ring for the rate rows, a sched_barrier per row
-// and per-level partials through write_sums. There is no block schedule: border rows belong to
-// slabs with a halo, which stay at one step per pass.
+// and per-level partials through write_sums. On a slab with a halo the interior rows run that
+// schedule beside the exchange and the K border rows of each side the BLOCK schedule after it
+// (closedk_block below, the counterpart of mm_fieldk.hpp's fieldk_block), which reads K ghost
+// rows of the state and K + 1 of the rate field (MM_CLOSED_HALO, include/mpimodel.h).
 //
 // The dependency cone. K steps of a cell read v within Chebyshev distance K and f within
 // K + 1: the share a cell at distance K gives at step 1 needs that cell's count of open
@@ -328,11 +330,93 @@ __device__ __forceinline__ void closedk_segment(const PassArgs& A, const CKLane&
     if (RED) write_sums<K, 1>(A, wid, lane, acc);
 }
 
-// K steps of a one-attribute closed rate-field diffusion per launch, segment schedule (A.th /
-// A.th_edge rows per wave, mm_passk.hpp seg_map; the wave map is mm_passk_kernel's). RED:
-// per-level sums of the owned cells, walls included, into partials[(partial_base + wave) * K
-// + level]. NT & 1: non-temporal stores. Two waves per SIMD at least: 256 registers per lane.
-template <int K, bool RED, int NT>
+// BLOCK schedule (mm_fieldk.hpp fieldk_block): TH output rows [rA, rB), the border rows of a
+// halo-split pass. Every one of the TH + 3K - 1 iterations is unrolled at compile time, so level
+// fill states, row offsets and block ownership are constants. There is no ring: the TH + 2K + 2
+// rate rows rA-K-1 .. rA+TH+K are loaded once and stay in registers (4 VGPRs per row and lane),
+// and the openness is built once, up front -- ck_open per rate row, ck_box per input row: TH + 2K
+// ring words and as many scalar body choices. Level j's m-th input is row (j-1) + m of the
+// block's input rows rA-K .. rA+TH+K-1, with that row's f, word and mode; the level itself is
+// ck_fill / ck_emit, so a block computes what a segment does, bit for bit. A block cut short by
+// the range's end (rB < rA + TH) reads zeros -- closed rows -- past its descriptors; the rows
+// past rB are neither stored nor summed.
+template <int K, int TH, bool RED>
+__device__ __forceinline__ void closedk_block(const PassArgs& A, const CKLane& c, long long wid,
+                                              int lane, int rA, int rB, unsigned voff,
+                                              unsigned soff) {
+    constexpr int NI = TH + 2 * K;       // input rows of the state
+    constexpr int NF = NI + 2;           // rate rows: row k is input row k - 1
+    constexpr int NIT = TH + 3 * K - 1;  // iterations
+    constexpr int U = 4;                 // state rows prefetched
+    double acc[K][1];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j][0] = 0.0;
+    const unsigned rowb = (unsigned)(A.pitch * 8);
+    const CKBufs<K> B(A, rA, rB);
+    const long long g0 = c.gx0 + rA - K;  // global row of input row 0
+    dv2 rawv[U], rawf[NF];
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+        if (k < U) rawv[k] = load_row(B.in, voff + k * rowb);
+        rawf[k] = load_row(B.fld, voff + k * rowb);
+    }
+    int word[NI], mode[NI];
+    {
+        int ob[NF], tri[NF];
+#pragma unroll
+        for (int k = 0; k < NF; ++k) ck_open(c, g0 - 1 + k, rawf[k], ob[k], tri[k]);
+#pragma unroll
+        for (int n = 0; n < NI; ++n)
+            ck_box(c, tri[n], tri[n + 1], tri[n + 2], ob[n + 1], word[n], mode[n]);
+    }
+    CKWin win[K];
+    double pend0[K], pend1[K];  // level j's row of the previous iteration: pend[j-1]
+
+#pragma unroll
+    for (int i = 0; i < NIT; ++i) {
+#pragma unroll
+        for (int j = K; j >= 1; --j) {  // descending: pend[j-2] is read before it is refilled
+            const int m = i - 3 * (j - 1);
+            if (m < 0 || m >= NI - 2 * (j - 1)) continue;  // compile-time
+            double v0, v1;
+            if (j == 1) {
+                v0 = rawv[i % U].x;
+                v1 = rawv[i % U].y;
+                if (i + U < NI) rawv[i % U] = load_row(B.in, voff + (i + U) * rowb);
+            } else {
+                v0 = pend0[j - 2];
+                v1 = pend1[j - 2];
+            }
+            const int row = (j - 1) + m;  // of the block's input rows; its rates: rawf[row + 1]
+            if (m < 2) {
+                ck_fill(m, win[j - 1], mode[row], word[row], v0, v1, rawf[row + 1].x,
+                        rawf[row + 1].y);
+                continue;
+            }
+            double w0, w1;
+            ck_emit(win[j - 1], mode[row], word[row], word[row - 1], v0, v1, rawf[row + 1].x,
+                    rawf[row + 1].y, w0, w1);
+            const int orow = m + j - K - 2;  // output row - rA (compile-time)
+            if (RED && orow >= 0 && orow < TH) ck_accum(acc[j - 1][0], rA + orow < rB, c, w0, w1);
+            if (j == K) {
+                store_row<0>(B.out, soff + orow * rowb, w0, w1);
+            } else {
+                pend0[j - 1] = w0;
+                pend1[j - 1] = w1;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);  // keep the row order: bounds the live registers
+    }
+    if (RED) write_sums<K, 1>(A, wid, lane, acc);
+}
+
+// K steps of a one-attribute closed rate-field diffusion per launch. MODE: kSeg = segment
+// schedule (A.th / A.th_edge rows per wave, mm_passk.hpp seg_map), else the block schedule with
+// MODE rows per wave (the border rows of a halo-split pass). The wave map is mm_passk_kernel's:
+// waves below A.waves_a work in rows [ra0, ra1), the others in [rb0, rb1). RED: per-level sums
+// of the owned cells, walls included, into partials[(partial_base + wave) * K + level]. NT & 1:
+// non-temporal stores (segment schedule). Two waves per SIMD at least: 256 registers per lane.
+template <int K, int MODE, bool RED, int NT>
 __global__ __launch_bounds__(kBlock, 2) void mm_closedk_kernel(const PassArgs A) {
     static_assert(K >= 2 && K <= kClosedMaxSteps, "mm_geom.hpp: kClosedMaxSteps");
     constexpr int L = (K + 2) / 2;            // halo lanes per side: 2L >= K + 1 columns
@@ -354,7 +438,13 @@ __global__ __launch_bounds__(kBlock, 2) void mm_closedk_kernel(const PassArgs A)
         rhi = A.rb1;
     }
     int strip, rA, rB;
-    seg_map(w, rlo, rhi, A.nstrips, A.th, A.th_edge, strip, rA, rB);
+    if (MODE == kSeg) {
+        seg_map(w, rlo, rhi, A.nstrips, A.th, A.th_edge, strip, rA, rB);
+    } else {
+        strip = (int)(w % A.nstrips);
+        rA = rlo + (int)(w / A.nstrips) * MODE;
+        rB = min(rA + MODE, rhi);
+    }
 
     const long long W = A.W;
     const long long c0 = (long long)strip * OC - 2 * L;  // first loaded column (even)
@@ -372,19 +462,26 @@ __global__ __launch_bounds__(kBlock, 2) void mm_closedk_kernel(const PassArgs A)
     c.own0 = store_lane;
     c.own1 = store_lane && y0 + 1 < W;
     c.known = lane == 0 ? 0xff00 : (lane == 63 ? 0x00ff : 0xffff);
-    closedk_segment<K, RED, NT>(A, c, wid, lane, rA, rB, voff, soff);
+    if constexpr (MODE == kSeg)
+        closedk_segment<K, RED, NT>(A, c, wid, lane, rA, rB, voff, soff);
+    else
+        closedk_block<K, MODE, RED>(A, c, wid, lane, rA, rB, voff, soff);
 }
 
-// The instances of one K: the segment schedule with or without non-temporal stores, each
-// with the step sums or without. nullptr for another kernel's key.
+// The instances of one K: the segment schedule with or without non-temporal stores, the
+// border blocks of kBorderRows rows (q.nt does not apply), each with the step sums or
+// without. nullptr for another kernel's key.
 template <int K>
 const KernelInst* closedk_inst(const InstKey& q) {
-    if (q.family != kInstClosedK || q.k != K || q.na != 1 || q.cols != 2 || !q.seg) return nullptr;
+    if (q.family != kInstClosedK || q.k != K || q.na != 1 || q.cols != 2) return nullptr;
+    if (!q.seg)
+        return q.red ? inst_of<mm_closedk_kernel<K, kBorderRows, true, 0>, kBlock>()
+                     : inst_of<mm_closedk_kernel<K, kBorderRows, false, 0>, kBlock>();
     if (q.nt)
-        return q.red ? inst_of<mm_closedk_kernel<K, true, 1>, kBlock>()
-                     : inst_of<mm_closedk_kernel<K, false, 1>, kBlock>();
-    return q.red ? inst_of<mm_closedk_kernel<K, true, 0>, kBlock>()
-                 : inst_of<mm_closedk_kernel<K, false, 0>, kBlock>();
+        return q.red ? inst_of<mm_closedk_kernel<K, kSeg, true, 1>, kBlock>()
+                     : inst_of<mm_closedk_kernel<K, kSeg, false, 1>, kBlock>();
+    return q.red ? inst_of<mm_closedk_kernel<K, kSeg, true, 0>, kBlock>()
+                 : inst_of<mm_closedk_kernel<K, kSeg, false, 0>, kBlock>();
 }
 
 }  // namespace

@@ -1028,9 +1028,13 @@ int check_run(mm_engine* e, long long nsteps, long long reduce_every, const char
     // that row's count, which reads the field one row further out. On a slab with a halo the
     // caller promises two ghost rows of the field at creation (MM_FIELD_HALO=2) and uploads
     // them on every side with a real neighbour; the plan itself never depends on either.
+    // K-step closed passes read one row more than their depth: K + 1 (MM_CLOSED_HALO).
+    if (e->pin.closed_k >= 2 && field_halo(e))
+        MM_TRY(check_field_rows(e, who, 0, mm::steps_per_launch(e->pin) + 1,
+                                "K-step closed passes read", "MM_CLOSED_HALO"));
     for (const mm::Pass& p : e->passes) {
         if (!p.closed || !field_halo(e)) continue;
-        if (e->pin.knobs.field_halo < 2)
+        if (mm::closed_field_promise(e->pin.knobs) < 2)
             return fail(MM_ERR_STATE, std::string(who) + ": a closed diffusion on a slab with a halo "
                                       "reads two ghost rows of the field: create the engine with "
                                       "MM_FIELD_HALO=2 (or more) and upload rows -2..h+1");

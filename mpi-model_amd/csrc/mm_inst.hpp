@@ -103,8 +103,8 @@ MM_INST_DECL(widea8_inst_n3_p0) MM_INST_DECL(widea8_inst_n3_p1)
 MM_INST_DECL(widea8_inst_n4_p0) MM_INST_DECL(widea8_inst_n4_p1)
 // mm_fieldk_k<K>.hip: the K-step rate-field kernel, one attribute, K = 2..kFieldMaxSteps
 MM_INST_DECL(fieldk_inst_k2) MM_INST_DECL(fieldk_inst_k3) MM_INST_DECL(fieldk_inst_k4)
-// mm_closedk_k<K>.hip: the K-step closed rate-field kernel, one attribute, segment schedule
-// only, K = 2..kClosedMaxSteps
+// mm_closedk_k<K>.hip: the K-step closed rate-field kernel, one attribute, K =
+// 2..kClosedMaxSteps
 MM_INST_DECL(closedk_inst_k2) MM_INST_DECL(closedk_inst_k3) MM_INST_DECL(closedk_inst_k4)
 #undef MM_INST_DECL
 
@@ -122,8 +122,9 @@ const KernelInst* find_inst(const InstKey& q);
 // segment schedule; else 4-row border blocks (a.th = kBorderRows); a.field[0] the rate field;
 // strips, row ranges, waves and partials as mm_passk_kernel's.
 // mm_closedk_kernel (one attribute, one closed rate-field diffusion, K 2..kClosedMaxSteps):
-// segment schedule only (a.seg); a.field[0] the rate field; a.nstrips = ceil(W /
-// closedk_out_cols(k)); row ranges, waves and partials as mm_passk_kernel's.
+// a.seg: segment schedule; else 4-row border blocks (a.th = kBorderRows); a.field[0] the rate
+// field; a.nstrips = ceil(W / closedk_out_cols(k)); row ranges, waves and partials as
+// mm_passk_kernel's.
 // hipErrorInvalidValue for a key no unit builds.
 hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s);
 

@@ -99,7 +99,8 @@ hipError_t launch_kstep(const InstKey& q, const PassArgs& a, hipStream_t s) {
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
         blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
     } else if (q.family == kInstClosedK) {
-        if (!a.field[0] || a.field_mask != 1 || !q.seg) return hipErrorInvalidValue;
+        if (!a.field[0] || a.field_mask != 1) return hipErrorInvalidValue;
+        if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;
         blocks = std::max<long long>(1, (a.waves_total + kWavesPerBlock - 1) / kWavesPerBlock);
     } else if (q.family == kInstPassK) {
         if (!q.seg && a.th != kBorderRows) return hipErrorInvalidValue;

@@ -51,6 +51,7 @@ const KnobRow kKnobRows[] = {
     {"MM_FIELD_HALO", 'i', 1, kFieldMaxSteps, [](Knobs& k, double v) { k.field_halo = (int)v; }},
     {"MM_CLOSED_STEPS", 'i', 0, kAny,
      [](Knobs& k, double v) { k.closed_steps = (int)std::min(v, (double)kClosedMaxSteps); }},
+    {"MM_CLOSED_HALO", 'i', 2, kClosedMaxSteps + 1, [](Knobs& k, double v) { k.closed_halo = (int)v; }},
     {"MM_WIDE_COLS", 'i', 4, kWide6Cols, [](Knobs& k, double v) { if (v != 5) k.wide_cols = (int)v; }},
 };
 
@@ -285,12 +286,18 @@ int field_k_for(const PlanIn& in, bool halo) {
     return k >= 2 ? k : 0;
 }
 
+int closed_field_promise(const Knobs& knobs) { return std::max(knobs.field_halo, knobs.closed_halo); }
+
 int closed_k_for(const PlanIn& in, bool halo) {
-    const int k = std::min(in.knobs.closed_steps, kClosedMaxSteps);
-    if (halo || !in.closed || !in.knobs.passk || k < 2 || in.pitch <= 0 ||
+    int k = std::min(in.knobs.closed_steps, kClosedMaxSteps);
+    if (!in.closed || !in.knobs.passk || k < 2 || in.pitch <= 0 ||
         closedk_max_rows(kClosedMaxSteps, in.pitch) < 64)
         return 0;
-    return k;
+    // a k-step pass reads k + 1 ghost rows of the field and sends k owned rows each way: the
+    // knobs and the chain's thinnest slab, never the rows uploaded or this slab's own.
+    // MM_CLOSED_HALO alone opts in: MM_FIELD_HALO keeps changing no plan of a closed program
+    if (halo) k = (int)std::min<long long>(std::min(k, in.knobs.closed_halo - 1), in.min_rows);
+    return k >= 2 ? k : 0;
 }
 
 bool kstep_ok(const PlanIn& in) { return fused_kind(in) || passk_ok(in); }
@@ -612,7 +619,8 @@ long long partials_need(const PlanIn& in) {
     // wave: K <= kMaxSteps for one attribute, K <= 2 for up to kMaxAttr; mm_fieldk_kernel,
     // segments of >= 8 rows over no more strips than these plus, split, one 4-row border
     // block per strip and side, K <= kFieldMaxSteps sums per wave; mm_closedk_kernel, segments
-    // of >= 8 rows over fewer strips still (closedk_out_cols), K <= kClosedMaxSteps sums per wave
+    // of >= 8 rows over fewer strips still (closedk_out_cols) plus, split, its 4-row border
+    // blocks, K <= kClosedMaxSteps sums per wave
     const long long ns1 = in.pitch / kStripCols;
     const long long need = (waves_for(ns1, in.h, 8) + 2 * waves_for(ns1, 2, 1) + 16) * kMaxAttr;
     const long long ns = ceil_div(in.W, passk_out_cols(kMaxSteps));

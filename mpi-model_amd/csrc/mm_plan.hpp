@@ -44,6 +44,12 @@ struct Knobs {
     int closed_steps = 0;    // steps per closed rate-field pass (MM_CLOSED_STEPS: 0 or 1 one step
                              // per pass, 2..kClosedMaxSteps that K on mm_closedk_kernel; no
                              // auto rule)
+    int closed_halo = 0;     // valid ghost rows of the rate field of a closed diffusion on each
+                             // side that has a neighbour, the caller's promise (MM_CLOSED_HALO,
+                             // 2..kClosedMaxSteps + 1; 0: unset): a K-step closed pass on a slab
+                             // with a halo reads K + 1 such rows, one more than MM_FIELD_HALO
+                             // reaches, and bounds its K by this knob alone; the one-step closed
+                             // pass's promise of 2 rows is max(field_halo, closed_halo)
     int wide_cols = 0;       // MM_WIDE_COLS: 6 the fused six-column K = 20 pass wherever its
                              // shape allows (wide6_on), 4 never; 0 auto: slabs of >= 2^27 cells
 };
@@ -73,8 +79,8 @@ struct PlanIn {
                              // and its passes fuse up to this many steps on mm_fieldk_kernel
                              // (the engine sets field_k_for; 0: off)
     int closed_k = 0;        // >= 2: the program is one closed rate-field diffusion of one
-                             // attribute on a slab without a halo, and its passes fuse up to this
-                             // many steps on mm_closedk_kernel (the engine sets closed_k_for; 0: off)
+                             // attribute, and its passes fuse up to this many steps on
+                             // mm_closedk_kernel (the engine sets closed_k_for; 0: off)
     Knobs knobs;
     int ncu = 0;             // compute units of the device
     // resident wave (kPassK, kFieldK, kClosedK) or workgroup (kWide) slots per CU of the instance that runs a
@@ -143,10 +149,18 @@ int field_steps_for(const PlanIn& in);
 // diffusion (in.closed): 0.
 int field_k_for(const PlanIn& in, bool halo);
 // PlanIn::closed_k of a program that may run on mm_closedk_kernel (one attribute, exactly one
-// closed diffusion -- the engine checks that): min(MM_CLOSED_STEPS, kClosedMaxSteps) where that
-// is 2 or more; 0 (one step per pass) with the knob unset, 0 or 1, with a halo (a chain, any
-// halo mode, MM_SELF_HALO), under MM_PASSK=0 and where closedk_max_rows < 64. No auto rule.
+// closed diffusion -- the engine checks that). Without a halo: min(MM_CLOSED_STEPS,
+// kClosedMaxSteps). With one (a chain, any halo mode, MM_SELF_HALO): min(that,
+// MM_CLOSED_HALO - 1, min_rows) -- a K-step pass reads K + 1 ghost rows of the rate field,
+// which the engine never exchanges and the caller promises, and sends K owned rows each way;
+// MM_FIELD_HALO changes no plan of a closed program, as before MM_CLOSED_HALO existed.
+// Under 2: 0 (one step per pass), as with the knob unset, 0 or 1, under MM_PASSK=0 and where
+// closedk_max_rows < 64. No auto rule. Reads the knobs, never the rows uploaded.
 int closed_k_for(const PlanIn& in, bool halo);
+// Ghost rows of the rate field the caller promised a closed diffusion on every side with a
+// neighbour: max(MM_FIELD_HALO, MM_CLOSED_HALO). The one-step closed pass needs 2 (the engine's
+// check; no plan reads this).
+int closed_field_promise(const Knobs& knobs);
 // A run advances in K-step passes of the program's only pass: passk_ok, field_k >= 2 or
 // closed_k >= 2.
 bool kstep_ok(const PlanIn& in);

@@ -101,7 +101,8 @@ void set_program(PlanIn& pin, const std::vector<Pass>& passes, bool halo, int th
                        !pin.chains;
     pin.field_k = alone ? field_k_for(pin, halo) : 0;
     // K-step closed passes (mm_closedk_kernel): one attribute, a program that is exactly one
-    // closed diffusion, a slab without a halo, and MM_CLOSED_STEPS asking for them
+    // closed diffusion, and MM_CLOSED_STEPS asking for them; with a halo K + 1 promised ghost
+    // rows of the field as well (MM_CLOSED_HALO) and a chain no thinner than K
     const bool closed_alone = na == 1 && p && p->field_mask == 1 && p->closed;
     pin.closed_k = closed_alone ? closed_k_for(pin, halo) : 0;
 }

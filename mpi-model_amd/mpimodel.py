@@ -328,7 +328,11 @@ class Engine:
     def add_diffuse_closed(self, attr):
         """Diffusion of `attr` by its rate field on a closed domain: cells of rate zero are
         walls that take no share, give none and keep their bits (MM_FLOW_DIFFUSE_CLOSED). A
-        slab of a chain is created with MM_FIELD_HALO=2 and uploads field rows -2..h+1."""
+        slab of a chain is created with MM_FIELD_HALO=2 and uploads field rows -2..h+1. Knob
+        notes: MM_CLOSED_STEPS=K (2..CLOSED_MAX_STEPS) fuses K steps per pass where the program
+        is this one flow on a one-attribute engine; on a slab with a halo it also takes
+        MM_CLOSED_HALO=K+1 (2..CLOSED_MAX_STEPS + 1, the promised ghost rows of the field; 2
+        or more also serves the one-step pass) and field rows -(K+1)..h+K uploaded."""
         check(lib().mm_add_flow(self.ptr, MM_FLOW_DIFFUSE_CLOSED, attr, attr, 0.0))
 
     def rate_field_upload(self, host, attr=0, row0=0):

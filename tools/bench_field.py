@@ -8,7 +8,7 @@ a launch, as a fraction of the 8 TB/s HBM peak; the arms alternate `--rounds` ti
 Needs a GPU; nothing here falls back.
 
   python tools/bench_field.py [--sizes 2048,4096,8192,16384] [--warmup 20] [--steps 200]
-                              [--rounds 3] [--self-halo] [--closed]
+                              [--rounds 3] [--self-halo] [--closed [--self-halo]]
 
 A size is N (an N x N grid) or HxW. Every arm also reports wall_step_us: host time per step
 of an untimed run of the same length (graph replay where the engine captures), the measure
@@ -35,6 +35,14 @@ over the field pass's (target: >= 0.9); a K arm's x_one_step is its time per ste
 one-step closed arm's of the same field (`closed` / `closed_disc`), beats_one_step whether it
 was below it in every round, pass_x its time per pass over that arm's, and over_fieldk the
 all-open pass's time over the field kind's pass of the same K.
+
+--closed --self-halo runs the closed arms split: every `closed*` engine is created with
+MM_HALO_RCCL, MM_SELF_HALO=1 and MM_CLOSED_HALO=K+1 (the one-step arms: 2), so its passes run
+interior segments beside the exchange and border blocks after it; `closedK_unsplit` and
+`closedK_disc_unsplit` are the same passes on an engine without a halo. The arms are compared
+by wall_step_us: a K arm's speedup is the split one-step arm's time per step over its own,
+beats_one_step whether it was below it in every round, over_unsplit its time over the unsplit
+arm's of the same K.
 
 Every arm times at least --steps steps, rounded up to a multiple of its K. Prints one JSON
 line per arm and round, then per size a summary line. For the K arms the summary holds the
@@ -97,16 +105,25 @@ def engine(H, W, k, self_halo=False):
     return e
 
 
-def closed_engine(H, W, disc, k=1):
+def closed_engine(H, W, disc, k=1, self_halo=False):
     """The closed pass on the field of the `field` arm, k steps per pass; disc: a disc of walls
-    of a quarter of the grid's cells in the middle."""
+    of a quarter of the grid's cells in the middle; self_halo: one RCCL rank that exchanges with
+    itself, created with MM_CLOSED_HALO = k + 1 (the split schedule)."""
     old = {name: os.environ.pop(name, None) for name in ("MM_PASSK", "MM_FIELD_STEPS", "MM_SELF_HALO",
-                                                         "MM_FIELD_HALO", "MM_CLOSED_STEPS")}
+                                                         "MM_FIELD_HALO", "MM_CLOSED_STEPS",
+                                                         "MM_CLOSED_HALO")}
+    env = {"MM_CLOSED_STEPS": str(k)}
+    if self_halo:
+        env.update(MM_SELF_HALO="1", MM_CLOSED_HALO=str(k + 1))
     try:
-        os.environ["MM_CLOSED_STEPS"] = str(k)
-        e = mm.Engine(H, W)
+        os.environ.update(env)
+        if self_halo:
+            e = mm.Engine(H, W, halo_mode=mm.MM_HALO_RCCL, comm_id_bytes=mm.comm_id())
+        else:
+            e = mm.Engine(H, W)
     finally:
-        os.environ.pop("MM_CLOSED_STEPS", None)
+        for name in env:
+            os.environ.pop(name, None)
         os.environ.update({name: v for name, v in old.items() if v is not None})
     e.fill_random(0)
     e.rate_field_fill(0.1)
@@ -123,6 +140,47 @@ def closed_engine(H, W, disc, k=1):
     want = (5, k, 1) if k >= 2 else (0, 1, 1)
     assert (info["kernel"], info["steps_per_launch"], info["n_passes"]) == want, info
     return e
+
+
+def run_closed_self_halo(size, a):
+    """The closed arms on one self-halo rank (split passes) beside the unsplit K-step arms,
+    compared by wall_step_us."""
+    H, W = shape_of(size)
+    engines, arms = {}, {}
+    for tail, disc in (("", False), ("_disc", True)):
+        engines["closed" + tail] = closed_engine(H, W, disc, 1, True)
+        arms["closed" + tail] = 1
+        for k in CLOSED_KS:
+            engines["closed%d%s" % (k, tail)] = closed_engine(H, W, disc, k, True)
+            engines["closed%d%s_unsplit" % (k, tail)] = closed_engine(H, W, disc, k)
+            arms["closed%d%s" % (k, tail)] = arms["closed%d%s_unsplit" % (k, tail)] = k
+    res = {name: [] for name in engines}
+    for rnd in range(a.rounds):
+        for name, e in engines.items():
+            r = measure(e, H * W, arms[name], a.warmup, a.steps)
+            res[name].append(r)
+            print(json.dumps({"arm": name, "self_halo": not name.endswith("_unsplit"), "round": rnd,
+                              "H": H, "W": W, **r}), flush=True)
+    for e in engines.values():
+        e.close()
+    out = {"summary": "closed rate-field passes, self-halo (split)", "H": H, "W": W,
+           "rounds": a.rounds, "arms": {}}
+    for name, rows in res.items():
+        out["arms"][name] = {key: span(rows, key) for key in ("pass_us", "step_us", "wall_step_us")}
+    for k in CLOSED_KS:
+        for tail in ("", "_disc"):
+            name, one, flat = "closed%d%s" % (k, tail), "closed" + tail, "closed%d%s_unsplit" % (k, tail)
+            arm = out["arms"][name]
+            arm["speedup"] = round(out["arms"][one]["wall_step_us"]["mean"] /
+                                   arm["wall_step_us"]["mean"], 3)
+            ratios = [c["wall_step_us"] / r["wall_step_us"] for r, c in zip(res[name], res[one])]
+            arm["speedup_range"] = [round(min(ratios), 2), round(max(ratios), 2)]
+            arm["beats_one_step"] = all(r["wall_step_us"] < c["wall_step_us"]
+                                        for r, c in zip(res[name], res[one]))
+            over = [r["wall_step_us"] / u["wall_step_us"] for r, u in zip(res[name], res[flat])]
+            arm["over_unsplit"] = [round(min(over), 3), round(max(over), 3)]
+    print(json.dumps(out), flush=True)
+    return out
 
 
 def run_closed(size, a):
@@ -294,7 +352,7 @@ def main():
     cells = lambda s: shape_of(s)[0] * shape_of(s)[1]  # noqa: E731
     if a.closed:
         for size in sizes:
-            run_closed(size, a)
+            (run_closed_self_halo if a.self_halo else run_closed)(size, a)
         return
     if a.self_halo:
         table = {size: run_self_halo(size, a) for size in sizes}
